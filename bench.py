@@ -15,9 +15,11 @@ batches of 10 as TTS.infer_batched feeds it.  One STEP = one pass over the whole
 configs[4] (e4m3 QKV / FFN operands in the batched decode step).
 
 Weights are seeded random tensors of the real architecture (no checkpoints exist offline).
-value = semantic tokens/s of the whole job end to end (AR + vocoder), all ranks; extra keys give the AR-only rate,
-the vocoder audio-s/s, p50 TTFT, per-kernel and step-level rooflines, the fp32 parity-mode rates and the CPU baseline
-(the oracle = a C/OpenMP restatement of the reference's CPU path, timed on this box's cores).
+value = semantic tokens/s of the whole job end to end (AR + vocoder), all ranks; extra keys give the AR-only rate and
+the vocoder audio-s/s.  A plain run sets up, warms up, times the steps and prints that line; --full adds what takes runs of
+its own: p50 TTFT, per-kernel and step-level rooflines, the cb32 sub-record, the fp32 parity-mode rates and the CPU baseline
+(the oracle = a C/OpenMP restatement of the reference's CPU path, timed on this box's cores).  --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy, for comparing two builds output for output.
 
 N>1: one process per GPU (torch.distributed, backend nccl == RCCL).  Utterances are independent; the only collective
 is the ONE broadcast of the reference-speaker embedding `ge` from rank 0 when the speaker is first seen (setup, not
@@ -80,6 +82,11 @@ def parse():
     ap.add_argument("--overlap", action="store_true", help="cb: vocoder batches on a side stream while the slot loop decodes (measured "
                     "+1 .. +4 %% end to end: the two share the chip) instead of after it in TTS.infer_batched's length-balanced order")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: single: the cb32 sub-record, "
+                    "TTFT, rooflines and per-kernel timings, the sampling / time-to-first-audio / fp32 extras; cb: the enc_p pass and the "
+                    "first-batch TTFT; both: the CPU baseline.  The --no-* options below narrow a --full run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the sampling / time-to-first-audio / fp32 extras")
     ap.add_argument("--no-cb32", action="store_true", help="single: skip the cb32 sub-record (32-slot continuous batching through the engine, "
@@ -210,6 +217,25 @@ def cpu_baseline(kind, version, timeout_s=300):
     except subprocess.TimeoutExpired:
         return {"value": None, "unit": "semantic_tokens/s", "cores": 0, "kind": "port",
                 "sample": "cpu baseline worker exceeded %ds" % timeout_s}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: tensor / array} -> d/<name>.npy; floating data as float32 (float64 stays float64), integers as float64"""
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for name, x in arrays.items():
+        x = x.detach().cpu() if torch.is_tensor(x) else torch.from_numpy(np.asarray(x))
+        x = x.double() if not x.is_floating_point() or x.dtype == torch.float64 else x.float()
+        out[name] = x.numpy()
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, x in out.items():
+        np.save(os.path.join(d, name + ".npy"), x)
+    log("outputs of the last timed step written to %s (%s)" % (d, ", ".join("%s %s" % (n, list(x.shape)) for n, x in out.items())))
 
 
 def _torch_dtype(name):
@@ -427,6 +453,7 @@ def run_single(a):
 
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(a.steps)]
     n_tok = [0]
+    last = {}
 
     def step(i, timed_idx):
         x, y, bert = reqs[i % len(reqs)]
@@ -439,11 +466,15 @@ def run_single(a):
         if timed_idx is not None:
             ev[timed_idx][2].record()
         n_tok[0] = tok.shape[-1]
+        if a.dump_outputs:
+            last["tokens"], last["audio"] = tok, audio
         return tok, audio
 
     log("models ready")
     elapsed = timed_region(a.steps, a.warmup, step, dev, dist)
     log("timed region done: %.3f s" % elapsed)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
     tokens_per_step = n_tok[0]
     assert tokens_per_step == N_NEW, "expected %d tokens per utterance, got %d" % (N_NEW, tokens_per_step)
     t_ar = sum(e[0].elapsed_time(e[1]) for e in ev) / 1e3 / a.steps
@@ -473,7 +504,7 @@ def run_single(a):
     # ContinuousBatchingEngine (shared request cursor, token exchange, vocoder stage dealt over the ranks, every request's
     # samples gathered on rank 0 INSIDE the timed step); at --gpus 8 this record is configs[3].  Every rank takes part.
     cb32 = None
-    if not a.no_cb32:
+    if a.full and not a.no_cb32:
         try:
             w = CBWorkload(a, world, rank, dev, dist, a.version, a.dtype, CB_SLOTS, CB_REQUESTS_PER_GPU, voc=voc, book=book, ge=ge)
             el = timed_region(a.cb32_steps, 1, w.step, dev, dist)
@@ -509,7 +540,7 @@ def run_single(a):
     if cb32 is not None:
         out["cb32"] = cb32
 
-    if rank == 0:
+    if rank == 0 and a.full:
         x, y, bert = reqs[0]
         rt = t2s._rt[1]
         # ---- p50 TTFT: prefill + first sample available on the host (ref-audio caches warm)
@@ -721,6 +752,7 @@ def run_single(a):
                     if cb.get("ar_tokens_per_s"):
                         ratios["fp32_mode_ar_only"] = f32["ar_tokens_per_s"] / cb["ar_tokens_per_s"]
                 out["speedup_vs_cpu_baseline_by_leg"] = ratios
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
@@ -811,6 +843,7 @@ class CBWorkload:
         self.bs = [torch.from_numpy(r[2]).to(dev) for r in reqs]
         self.acc = {"tok": 0, "frames": 0, "t_ar": 0.0, "t_voc": 0.0, "steps": 0, "kv_rows": 0, "mine": 0, "gathered_samples": 0, "timed": 0}
         self.costs = [int(x.shape[0]) + int(y.shape[0]) + int(n) for x, y, n in zip(self.xs, self.ys, self.new_tok)] if a.lpt_budget else None
+        self.keep_last, self.last = False, None        # keep_last: step() keeps what it returned for dump()
 
     def vocode(self, tokens):
         """TTS.infer_batched's vocoder stage (TTS.py:705-764, tts.py): length-balanced order over ALL requests, time-concatenated
@@ -887,12 +920,17 @@ class CBWorkload:
                 acc["stub_ordered"] = acc.get("stub_ordered", 0) + len(full)
             if timed_idx is not None and full is not None:
                 acc["gathered_samples"] += int(sum(t.numel() for t in full))
+            if self.keep_last:
+                self.last = {"request_ids": list(range(self.n_req)), "tokens": tokens, "audio": full}
             del full, audio
         else:
             res, pred, idx = eng.run_overlapped(self.xs, self.ys, self.bs, self.vocode_batch, batch=10, costs=self.costs, top_k=1,
                                                 max_new_tokens=self.new_tok, async_refill=not a.sync_refill)
             s1 = time.perf_counter()
             frames = int(sum(res.values()))
+            if self.keep_last:        # the overlapped loop returns no audio, and only this rank's requests
+                order = sorted(range(len(pred)), key=lambda j: int(idx[j]))
+                self.last = {"request_ids": [int(idx[j]) for j in order], "tokens": [pred[j] for j in order], "audio": None}
         _sync(dev); s2 = time.perf_counter()
         if timed_idx is not None:
             acc["tok"] += int(sum(len(p) for p in pred)); acc["frames"] += frames
@@ -904,6 +942,18 @@ class CBWorkload:
             if t2s.last_stats.get("compactions"):
                 acc["compactions"] = [list(c) for c in t2s.last_stats["compactions"]]
             acc["passes"] = acc.get("passes", 0) + int(t2s.last_stats.get("passes", 0))
+
+    def dump(self, d):
+        """--dump-outputs on rank 0: the last timed step's tokens of every request (request order, concatenated) with their lengths, and
+        a fixed seeded sample of 4 Mi of the samples gathered on rank 0 (all of them are ~300 MB at the default size)"""
+        last = self.last
+        arrays = {"request_ids": last["request_ids"], "token_lengths": [int(t.numel()) for t in last["tokens"]],
+                  "tokens": torch.cat([t.reshape(-1).cpu() for t in last["tokens"]])}
+        if last["audio"] is not None:
+            audio = torch.cat([t.reshape(-1).float() for t in last["audio"]])
+            pick = np.sort(np.random.default_rng(0).integers(0, audio.numel(), size=min(audio.numel(), 1 << 22)))
+            arrays["audio_sample"] = audio[torch.from_numpy(pick).to(audio.device)]
+        dump_outputs(d, arrays)
 
     def refill_label(self):
         """what the slot loop that was measured does when a slot ends -- read from the decoder, not assumed"""
@@ -994,13 +1044,17 @@ def run_cb(a):
     world, rank, dev, dist = setup_dist(a)
     from gsv_tts_lite_amd import synth
     w = CBWorkload(a, world, rank, dev, dist, a.version, a.dtype, a.slots, a.requests)
+    w.keep_last = bool(a.dump_outputs)
     log("models ready")
     elapsed = timed_region(a.steps, a.warmup, w.step, dev, dist)
     log("timed region done: %.3f s" % elapsed)
+    if a.dump_outputs and rank == 0:
+        w.dump(a.dump_outputs)
+    w.last = None
     out = w.record(elapsed, a.steps, a.warmup)
     value = out["value"]
     t2s, eng, xs, ys, bs, n_req = w.t2s, w.eng, w.xs, w.ys, w.bs, w.n_req
-    if (not a.no_extras) and (not a.overlap):
+    if a.full and (not a.no_extras) and (not a.overlap):
         # one more pass over the queue with the vocoder stage as TTS.infer_batched runs it: decode() on the requests' own tokens
         # (every rank takes part: the token exchange is a collective)
         try:
@@ -1029,7 +1083,7 @@ def run_cb(a):
             del vq
         except Exception as e:  # noqa: BLE001
             log("value_with_enc_p pass failed: %r" % (e,))
-    if rank == 0 and not a.no_extras:
+    if rank == 0 and a.full and not a.no_extras:
         # BASELINE's "p50 TTFT ... bs=32": the first `slots` requests of the queue arrive together -> packed prompt pass of
         # all of them + the first decode step (every request's first token exists), outside the timed region
         try:
@@ -1049,7 +1103,7 @@ def run_cb(a):
             out["ttft_ms_p50_first_batch"] = None
             log("first-batch TTFT failed: %r" % (e,))
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("cpu baseline (subprocess) ...")
             cb = cpu_baseline("cb", a.version)
             out["cpu_baseline"] = cb

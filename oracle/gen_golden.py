@@ -472,12 +472,85 @@ def gen_sola():
     print("sola offsets:", [int(out["offset_%d" % k]) for k in range(len(SOLA_CASES))])
 
 
+def gen_loader():
+    """loader.json / loader.npz: what the reference's Loader makes of the checkpoint files tests/test_loader_reference.py writes
+    (the test module builds them; it is loaded from there so both sides build the same files).  Every recorded fact is checked
+    here against the reference's own output before it is written."""
+    import hashlib
+    import importlib.util
+    import json
+    import tempfile
+    import types
+    import pathlib
+    from safetensors.torch import load_model
+    spec = importlib.util.spec_from_file_location("loader_cases", os.path.join(ROOT, "tests", "test_loader_reference.py"))
+    T = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(T)
+    import gsv_tts.Loader as RL
+    from gsv_tts.GPT_SoVITS.SoVITS.models import SynthesizerTrn
+    from gsv_tts_lite_amd import loader
+    cpu = types.SimpleNamespace(device=torch.device("cpu"), dtype=torch.float32, use_flash_attn=False, gpt_cache=[(1, 64)], sovits_cache=[])
+    out, scales = {}, {}
+    with tempfile.TemporaryDirectory() as td:
+        td = pathlib.Path(td)
+        # GPT: every reference key -> the upstream key whose tensor it holds; the product's safetensors directory read back by it
+        cfg, up = T.gpt_upstream_checkpoint()
+        torch.save({"config": cfg, "weight": up}, str(td / "s1.ckpt"))
+        ref = RL.get_gpt_weights(str(td / "s1.ckpt"), cpu)
+        state = {}
+        for k, v in ref.t2s_model.state_dict().items():
+            state[k] = next(u for u, t in up.items() if t.shape == v.shape and torch.equal(t, v))
+        d = loader.convert_to_safetensors(str(td / "s1.ckpt"), str(td / "s1_dir"))
+        ref2 = RL.get_gpt_weights(d, cpu)
+        for k, v in ref2.t2s_model.state_dict().items():
+            assert torch.equal(v, up[state[k]]), k
+        out["gpt"] = {"config": ref.config, "state": state}
+        # SoVITS: the reference module's manifest, then its loader on the checkpoint built from it
+        out["sovits"] = {}
+        for version, head in T.SOVITS_CASES:
+            hps = synth.sovits_hps(version)
+            m = SynthesizerTrn(hps["data"]["filter_length"] // 2 + 1, hps["train"]["segment_size"] // hps["data"]["hop_length"],
+                               n_speakers=hps["data"]["n_speakers"], **{**hps["model"], "version": version})
+            manifest = [[k, list(v.shape)] for k, v in m.state_dict().items()]
+            assert all(v.dtype == torch.float32 for v in m.state_dict().values())
+            del m
+            sd = T.sovits_checkpoint(td / "s2.pth", version, head, manifest)
+            r = RL.get_sovits_weights(str(td / "s2.pth"), cpu)
+            ref_sd = r.vq_model.state_dict()
+            hot = [k for k in ref_sd if k.startswith(("dec.", "flow.", "enc_p.", "ref_enc.", "quantizer.", "ssl_proj.", "sv_emb.", "prelu."))]
+            folded = [k for k in hot if k not in sd]
+            for k in hot:
+                if k in sd:
+                    assert torch.equal(ref_sd[k], sd[k]), k
+                else:    # torch.nn.utils.remove_weight_norm: _weight_norm(v, g, dim 0) = v * (g / norm)
+                    g, v = sd[k + "_g"], sd[k + "_v"]
+                    s = g / torch._weight_norm_interface(v, g, 0)[1]
+                    assert torch.equal(v * s, ref_sd[k]), k
+                    scales[version + "/" + k] = s.numpy()
+            out["sovits"][version] = {"version": r.hps.model.version, "manifest": manifest, "hot": hot, "folded": folded}
+            del r, ref_sd, sd
+        out["hash_pretrained"] = dict(RL.hash_pretrained_dict)
+        out["head2version"] = {k.decode(): v for k, v in RL.head2version.items()}
+        out["md5_probes"] = {}
+        for n in (100, 8192, 20000):
+            (td / "probe").write_bytes(T.md5_probe_bytes(n))
+            out["md5_probes"][str(n)] = RL.get_hash_from_file(str(td / "probe"))
+            assert out["md5_probes"][str(n)] == hashlib.md5(T.md5_probe_bytes(n)[:8192]).hexdigest()
+    out["meta"] = META
+    with open(os.path.join(GOLD, "loader.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    np.savez_compressed(os.path.join(GOLD, "loader.npz"), **scales)
+    print("loader: %d GPT keys, %s SoVITS hot / folded keys" % (
+        len(out["gpt"]["state"]), {v: (len(o["hot"]), len(o["folded"])) for v, o in out["sovits"].items()}))
+
+
 if __name__ == "__main__":
     tqdm.tqdm.__init__ = functools.partialmethod(tqdm.tqdm.__init__, disable=True)
     torch.manual_seed(0)
     T2S, sample, Syn = import_reference()
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["layers", "infer", "batched", "stream", "sample", "vocoder", "decode", "subtitles", "refaudio", "facade", "sola"]
+    which = sys.argv[1:] or ["layers", "infer", "batched", "stream", "sample", "vocoder", "decode", "subtitles", "refaudio", "facade", "sola",
+                             "loader"]
     if "layers" in which: gen_t2s_layers(T2S)
     if "infer" in which: gen_t2s_infer(T2S)
     if "batched" in which: gen_t2s_batched(T2S)
@@ -489,3 +562,4 @@ if __name__ == "__main__":
     if "refaudio" in which: gen_refaudio(Syn)
     if "facade" in which: gen_facade()
     if "sola" in which: gen_sola()
+    if "loader" in which: gen_loader()

@@ -2,8 +2,8 @@
 
 Only usable in the build container, where /root/reference exists.  It never
 travels to the GPU box: nothing under tests/ -m gpu, smoke() or bench.py may
-import this module.  Used by oracle/gen_golden.py (fixture generation) and by
-the `reference`-marked CPU tests that pin the C/numpy oracle to the reference.
+import this module, and no test does: tests read what it produced from tests/golden/.
+Used by oracle/gen_golden.py (fixture generation).
 
 The reference's top-level package `gsv_tts/__init__.py` pulls in `av` and
 `torchaudio`, which are absent here; its hot-path modules import fine when the

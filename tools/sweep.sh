@@ -7,12 +7,12 @@ O=$R/gpurun_out/sweep; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() { echo "== $*" >&2; "$@"; }
 # 1. default bench line (configs[1]) and its rocprofv3 summary
-run timeout 900 python $R/bench.py > $O/bench_line.json 2> $O/bench_line.log
-rm -rf /tmp/p1; run timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-cb32 > /dev/null 2> $O/prof_bench.log
+run timeout 900 python $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.log
+rm -rf $TMPDIR/p1; run timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p1 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-cb32 > /dev/null 2> $O/prof_bench.log
 f=$(find /tmp/p1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -40 "$f" > $O/rocprofv3_kernel_stats.csv
 # 2. HBM / fabric traffic: two PMC passes (counters only, no tracing beyond kernel dispatch)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/pm_$c; run timeout 900 rocprofv3 --pmc $c --output-format csv -d /tmp/pm_$c -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-cb32 > /dev/null 2> $O/pmc_$c.log
+  rm -rf $TMPDIR/pm_$c; run timeout 900 rocprofv3 --pmc $c --output-format csv -d $TMPDIR/pm_$c -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-cb32 > /dev/null 2> $O/pmc_$c.log
 done
 # ... and the batched decode step of the cb32 record (32 sequences, kv ~ 350-450)
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -23,17 +23,17 @@ ff=$(find /tmp/pm_FETCH_SIZE -name "*counter_collection.csv" | head -1); fw=$(fi
 sf=$(find /tmp/ps_FETCH_SIZE -name "*counter_collection.csv" | head -1); sw=$(find /tmp/ps_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 [ -n "$ff" ] && [ -n "$fw" ] && python $R/tools/pmc_traffic.py "$ff" "$fw" $O/traffic.json $sf $sw > $O/traffic_table.txt 2>&1
 # 3. continuous batching lines
-run timeout 900 python $R/bench.py --workload cb --version v2ProPlus > $O/cb_configs2.json 2> $O/cb_configs2.log
-run timeout 900 python $R/bench.py --workload cb --version v2ProPlus --sync-refill --no-cpu-baseline > $O/cb_configs2_sync_refill.json 2> /dev/null
-run timeout 900 python $R/bench.py --workload cb --version v2ProPlus --lpt-budget --no-cpu-baseline > $O/cb_configs2_lpt_budget.json 2> /dev/null
-run timeout 900 python $R/bench.py --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32.json 2> /dev/null
-GSV_REFILL_AHEAD=0 run timeout 900 python $R/bench.py --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32_staged_loop.json 2> /dev/null
-GSV_TAIL_LEVELS=0 run timeout 900 python $R/bench.py --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32_no_tail_compaction.json 2> /dev/null
-run timeout 900 python $R/bench.py --workload cb --version v2ProPlus --slots 64 --no-cpu-baseline > $O/cb_bf16_bs64.json 2> /dev/null
-run timeout 900 python $R/bench.py --workload cb --version v2ProPlus --slots 64 --dtype fp8 --no-cpu-baseline > $O/cb_fp8_bs64.json 2> /dev/null
+run timeout 900 python $R/bench.py --full --workload cb --version v2ProPlus > $O/cb_configs2.json 2> $O/cb_configs2.log
+run timeout 900 python $R/bench.py --full --workload cb --version v2ProPlus --sync-refill --no-cpu-baseline > $O/cb_configs2_sync_refill.json 2> /dev/null
+run timeout 900 python $R/bench.py --full --workload cb --version v2ProPlus --lpt-budget --no-cpu-baseline > $O/cb_configs2_lpt_budget.json 2> /dev/null
+run timeout 900 python $R/bench.py --full --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32.json 2> /dev/null
+GSV_REFILL_AHEAD=0 run timeout 900 python $R/bench.py --full --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32_staged_loop.json 2> /dev/null
+GSV_TAIL_LEVELS=0 run timeout 900 python $R/bench.py --full --workload cb --version v2Pro --no-cpu-baseline > $O/cb_v2pro_bs32_no_tail_compaction.json 2> /dev/null
+run timeout 900 python $R/bench.py --full --workload cb --version v2ProPlus --slots 64 --no-cpu-baseline > $O/cb_bf16_bs64.json 2> /dev/null
+run timeout 900 python $R/bench.py --full --workload cb --version v2ProPlus --slots 64 --dtype fp8 --no-cpu-baseline > $O/cb_fp8_bs64.json 2> /dev/null
 # N > 1 through the bench's own launcher (no torchrun around it): two ranks on this box's one GPU, gloo
-run timeout 900 python $R/bench.py --gpus 2 --workload cb --share-gpu --dist-backend gloo --steps 1 --warmup 1 --requests 64 --no-cpu-baseline 2> $O/cb_2ranks.log | grep '^{' > $O/cb_2ranks_bare_launch.json
-rm -rf /tmp/p2; run timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p2 -- python $R/bench.py --workload cb --version v2ProPlus --steps 1 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2>&1
+run timeout 900 python $R/bench.py --full --gpus 2 --workload cb --share-gpu --dist-backend gloo --steps 1 --warmup 1 --requests 64 --no-cpu-baseline 2> $O/cb_2ranks.log | grep '^{' > $O/cb_2ranks_bare_launch.json
+rm -rf $TMPDIR/p2; run timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p2 -- python $R/bench.py --full --workload cb --version v2ProPlus --steps 1 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2>&1
 f=$(find /tmp/p2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -40 "$f" > $O/rocprofv3_kernel_stats_cb_configs2.csv
 # 4. raw step times
 ( for b in 1 2 4 8 16 17 24 32 33 40 64 128 256; do timeout 300 python $R/tools/step_time.py $b bf16 | grep step; done
