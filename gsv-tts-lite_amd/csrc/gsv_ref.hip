@@ -1,4 +1,5 @@
-// C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section); kernels in refaudio.h.
+// C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section; kernels in refaudio.h) and of
+// CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +11,7 @@
 
 #include "../../include/gsv_tts_hip.h"
 #include "gsv_error.h"
+#include "hubert.h"
 #include "refaudio.h"
 
 using namespace gsv;
@@ -269,6 +271,278 @@ int gsv_ref_extract_latent(gsv_ref* h, const float* ssl, int n_ssl, int64_t* cod
     rowsq_kernel<<<(To + 3) / 4, 256, 0, st>>>(Y, Dm, To, Dm, x2);
     nearest_code_kernel<<<(To + 3) / 4, 256, 0, st>>>(dot, x2, h->e2, To, c.bins, reinterpret_cast<long long*>(codes), margin);
     if (bad) return abi_fail(GSV_ERR_HIP, "ref: an extract_latent launch failed");
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// CN-HuBERT
+// ------------------------------------------------------------------------------------------------------------------
+struct gsv_hubert {
+    gsv_hubert_config cfg;
+    std::map<std::string, std::pair<float*, int64_t>> t;   // loaded tensors (device, fp32)
+    bool finalized = false;
+    // derived at finalize
+    float* w_conv[GSV_HUBERT_MAX_CONV] = {};                 // conv i >= 1 as [cout][k][cin]
+    float* w_pos = nullptr;                                 // folded weight norm, [H][k][H/G]
+    std::vector<float*> w_qkv, b_qkv;                       // per layer [3H][H], [3H] (q, k, v)
+    std::vector<void*> owned;
+};
+
+namespace {
+
+const float* HT(gsv_hubert* h, const std::string& name) { return h->t.at(name).first; }
+
+int hub_alloc(gsv_hubert* h, float** p, size_t floats) {
+    RCHK(hipMalloc(reinterpret_cast<void**>(p), floats * sizeof(float)));
+    h->owned.push_back(*p);
+    return GSV_OK;
+}
+
+// frame counts after every conv of the feature encoder; false when the input is too short for one
+bool hub_frames(const gsv_hubert_config& c, int n, int* T) {
+    int len = n;
+    for (int i = 0; i < c.n_conv; ++i) {
+        if (len < c.conv_kernel[i]) return false;
+        len = (len - c.conv_kernel[i]) / c.conv_stride[i] + 1;
+        T[i] = len;
+    }
+    return true;
+}
+
+std::string hub_layer(int l, const char* rest) { return "encoder.layers." + std::to_string(l) + "." + rest; }
+
+// workspace carve-up of one forward, in floats (256-byte slots); the same walk sizes and assigns it
+struct HubWs {
+    float *act[2], *pmean, *pm2, *gmean, *gscale, *hid, *pg, *part, *x, *tmp, *qkv, *att, *ffn;
+    size_t total;
+};
+HubWs hub_carve(const gsv_hubert_config& c, const int* T, float* base) {
+    HubWs w;
+    size_t off = 0;
+    auto take = [&](size_t n) { float* r = base ? base + off : nullptr; off += up(n); return r; };
+    size_t a0 = 0, a1 = 0;   // ping-pong: conv i writes act[i & 1]
+    for (int i = 0; i < c.n_conv; ++i) {
+        size_t& a = (i & 1) ? a1 : a0;
+        a = std::max(a, (size_t)T[i] * c.conv_dim[i]);
+    }
+    const int C0 = c.conv_dim[0], nch = (T[0] + GN_ROWS - 1) / GN_ROWS;
+    const size_t Th = T[c.n_conv - 1], H = c.hidden;
+    w.act[0] = take(a0);
+    w.act[1] = take(a1);
+    w.pmean = take((size_t)nch * C0);
+    w.pm2 = take((size_t)nch * C0);
+    w.gmean = take(C0);
+    w.gscale = take(C0);
+    w.hid = take(Th * H);
+    w.pg = take((Th + c.pos_k - 1) * H);
+    w.part = take(POS_SPLIT * Th * H);
+    w.x = take(Th * H);
+    w.tmp = take(Th * H);
+    w.qkv = take(Th * 3 * H);
+    w.att = take(Th * H);
+    w.ffn = take(Th * c.ffn);
+    w.total = off;
+    return w;
+}
+
+int ln(hipStream_t st, const float* x, float* y, int rows, int C, const float* g, const float* b, float eps) {
+    ln_rows_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, y, rows, C, g, b, eps);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsv_hubert_create(const gsv_hubert_config* cfg, gsv_hubert** out) {
+    if (!cfg || !out) return abi_fail(GSV_ERR_ARG, "null argument");
+    const gsv_hubert_config& c = *cfg;
+    if (c.hidden < 64 || c.hidden % 64 || c.hidden > 64 * LN_MAX_NPL)
+        return abi_fail(GSV_ERR_ARG, "hubert: hidden %d unsupported (a multiple of 64 up to %d)", c.hidden, 64 * LN_MAX_NPL);
+    if (c.n_head < 1 || c.hidden != 64 * c.n_head)
+        return abi_fail(GSV_ERR_ARG, "hubert: %d heads over hidden %d unsupported (the attention kernel needs head dim 64)", c.n_head, c.hidden);
+    if (c.n_layer < 0 || c.ffn < 1) return abi_fail(GSV_ERR_ARG, "hubert: n_layer %d / ffn %d unsupported", c.n_layer, c.ffn);
+    if (c.n_conv < 1 || c.n_conv > GSV_HUBERT_MAX_CONV) return abi_fail(GSV_ERR_ARG, "hubert: %d feature-encoder convs (1..%d)", c.n_conv, GSV_HUBERT_MAX_CONV);
+    for (int i = 0; i < c.n_conv; ++i) {
+        if (c.conv_dim[i] < 64 || c.conv_dim[i] % 64 || c.conv_dim[i] > 64 * LN_MAX_NPL)
+            return abi_fail(GSV_ERR_ARG, "hubert: conv_dim[%d] = %d unsupported (a multiple of 64 up to %d)", i, c.conv_dim[i], 64 * LN_MAX_NPL);
+        if (c.conv_kernel[i] < 1 || c.conv_stride[i] < 1)
+            return abi_fail(GSV_ERR_ARG, "hubert: conv %d kernel %d / stride %d unsupported", i, c.conv_kernel[i], c.conv_stride[i]);
+    }
+    if (c.pos_k < 2 || c.pos_k % 2 || c.pos_groups < 1 || c.hidden % c.pos_groups)
+        return abi_fail(GSV_ERR_ARG, "hubert: positional conv k %d / groups %d unsupported (even k, groups dividing hidden)", c.pos_k, c.pos_groups);
+    if (!(c.eps > 0.f)) return abi_fail(GSV_ERR_ARG, "hubert: layer_norm_eps must be > 0");
+    gsv_hubert* h = new gsv_hubert();
+    h->cfg = c;
+    *out = h;
+    return GSV_OK;
+}
+
+int gsv_hubert_destroy(gsv_hubert* h) {
+    if (!h) return GSV_OK;
+    for (auto& kv : h->t) (void)hipFree(kv.second.first);
+    for (void* p : h->owned) (void)hipFree(p);
+    delete h;
+    return GSV_OK;
+}
+
+int gsv_hubert_load_tensor(gsv_hubert* h, const char* name, const float* data, int64_t numel, void* stream) {
+    if (!h || !name || !data || numel < 1) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return abi_fail(GSV_ERR_STATE, "hubert: load after finalize");
+    std::string n(name);
+    if (n == "encoder.pos_conv_embed.conv.parametrizations.weight.original0") n = "encoder.pos_conv_embed.conv.weight_g";
+    if (n == "encoder.pos_conv_embed.conv.parametrizations.weight.original1") n = "encoder.pos_conv_embed.conv.weight_v";
+    if (n.rfind("feature_extractor.", 0) != 0 && n.rfind("feature_projection.", 0) != 0 && n.rfind("encoder.", 0) != 0)
+        return abi_fail(GSV_ERR_ARG, "hubert: unknown tensor %s", name);
+    float* d = nullptr;
+    RCHK(hipMalloc(reinterpret_cast<void**>(&d), numel * sizeof(float)));
+    RCHK(hipMemcpyAsync(d, data, numel * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+    auto it = h->t.find(n);
+    if (it != h->t.end()) (void)hipFree(it->second.first);
+    h->t[n] = {d, numel};
+    return GSV_OK;
+}
+
+int gsv_hubert_finalize(gsv_hubert* h, void* stream) {
+    if (!h) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return GSV_OK;
+    const gsv_hubert_config& c = h->cfg;
+    const int64_t H = c.hidden, F = c.ffn, C0 = c.conv_dim[0], CL = c.conv_dim[c.n_conv - 1], cg = H / c.pos_groups;
+    std::vector<std::pair<std::string, int64_t>> need = {
+        {"feature_extractor.conv_layers.0.conv.weight", C0 * c.conv_kernel[0]},
+        {"feature_extractor.conv_layers.0.layer_norm.weight", C0}, {"feature_extractor.conv_layers.0.layer_norm.bias", C0},
+        {"feature_projection.layer_norm.weight", CL}, {"feature_projection.layer_norm.bias", CL},
+        {"feature_projection.projection.weight", H * CL}, {"feature_projection.projection.bias", H},
+        {"encoder.pos_conv_embed.conv.weight_g", c.pos_k}, {"encoder.pos_conv_embed.conv.weight_v", H * cg * c.pos_k},
+        {"encoder.pos_conv_embed.conv.bias", H},
+        {"encoder.layer_norm.weight", H}, {"encoder.layer_norm.bias", H},
+    };
+    for (int i = 1; i < c.n_conv; ++i)
+        need.push_back({"feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight",
+                        (int64_t)c.conv_dim[i] * c.conv_dim[i - 1] * c.conv_kernel[i]});
+    for (int l = 0; l < c.n_layer; ++l) {
+        for (const char* p : {"attention.q_proj", "attention.k_proj", "attention.v_proj", "attention.out_proj"}) {
+            need.push_back({hub_layer(l, p) + ".weight", H * H});
+            need.push_back({hub_layer(l, p) + ".bias", H});
+        }
+        need.push_back({hub_layer(l, "feed_forward.intermediate_dense.weight"), F * H});
+        need.push_back({hub_layer(l, "feed_forward.intermediate_dense.bias"), F});
+        need.push_back({hub_layer(l, "feed_forward.output_dense.weight"), H * F});
+        need.push_back({hub_layer(l, "feed_forward.output_dense.bias"), H});
+        for (const char* p : {"layer_norm.weight", "layer_norm.bias", "final_layer_norm.weight", "final_layer_norm.bias"})
+            need.push_back({hub_layer(l, p), H});
+    }
+    for (const auto& n : need) {
+        auto it = h->t.find(n.first);
+        if (it == h->t.end()) return abi_fail(GSV_ERR_STATE, "hubert: tensor %s was not loaded", n.first.c_str());
+        if (it->second.second != n.second)
+            return abi_fail(GSV_ERR_ARG, "hubert: tensor %s has %lld elements, expected %lld", n.first.c_str(),
+                            (long long)it->second.second, (long long)n.second);
+    }
+    hipStream_t st = S(stream);
+    int rc;
+    for (int i = 1; i < c.n_conv; ++i) {
+        const int co = c.conv_dim[i], ci = c.conv_dim[i - 1], k = c.conv_kernel[i];
+        const long long nw = (long long)co * ci * k;
+        if ((rc = hub_alloc(h, &h->w_conv[i], nw))) return rc;
+        conv_weight_kc_kernel<<<(unsigned)((nw + 255) / 256), 256, 0, st>>>(
+            HT(h, "feature_extractor.conv_layers." + std::to_string(i) + ".conv.weight"), h->w_conv[i], co, ci, k);
+    }
+    float* norm = nullptr;
+    const long long npos = H * cg * c.pos_k;
+    if ((rc = hub_alloc(h, &h->w_pos, npos)) || (rc = hub_alloc(h, &norm, c.pos_k))) return rc;
+    wn_tap_norm_kernel<<<c.pos_k, 256, 0, st>>>(HT(h, "encoder.pos_conv_embed.conv.weight_v"), H * cg, c.pos_k, norm);
+    wn_fold_kc_kernel<<<(unsigned)((npos + 255) / 256), 256, 0, st>>>(HT(h, "encoder.pos_conv_embed.conv.weight_v"),
+                                                                     HT(h, "encoder.pos_conv_embed.conv.weight_g"), norm, h->w_pos, (int)H, (int)cg, c.pos_k);
+    h->w_qkv.assign(c.n_layer, nullptr);
+    h->b_qkv.assign(c.n_layer, nullptr);
+    for (int l = 0; l < c.n_layer; ++l) {
+        if ((rc = hub_alloc(h, &h->w_qkv[l], 3 * H * H)) || (rc = hub_alloc(h, &h->b_qkv[l], 3 * H))) return rc;
+        const char* p[3] = {"attention.q_proj", "attention.k_proj", "attention.v_proj"};
+        for (int j = 0; j < 3; ++j) {
+            RCHK(hipMemcpyAsync(h->w_qkv[l] + j * H * H, HT(h, hub_layer(l, p[j]) + ".weight"), H * H * 4, hipMemcpyDeviceToDevice, st));
+            RCHK(hipMemcpyAsync(h->b_qkv[l] + j * H, HT(h, hub_layer(l, p[j]) + ".bias"), H * 4, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    RCHK(hipGetLastError());
+    h->finalized = true;
+    return GSV_OK;
+}
+
+int gsv_hubert_frames(gsv_hubert* h, int n_samples) {
+    if (!h) return 0;
+    int T[GSV_HUBERT_MAX_CONV];
+    return hub_frames(h->cfg, n_samples, T) ? T[h->cfg.n_conv - 1] : 0;
+}
+
+size_t gsv_hubert_workspace(gsv_hubert* h, int n_samples) {
+    if (!h) return 0;
+    int T[GSV_HUBERT_MAX_CONV];
+    if (!hub_frames(h->cfg, n_samples, T)) return 0;
+    return sizeof(float) * hub_carve(h->cfg, T, nullptr).total;
+}
+
+int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* ssl, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    if (!h || !audio || !ssl || !workspace) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (!h->finalized) return abi_fail(GSV_ERR_STATE, "hubert: not finalized");
+    const gsv_hubert_config& c = h->cfg;
+    int T[GSV_HUBERT_MAX_CONV];
+    if (!hub_frames(c, n_samples, T)) return abi_fail(GSV_ERR_ARG, "hubert: %d samples are too short for the feature encoder", n_samples);
+    if (workspace_bytes < gsv_hubert_workspace(h, n_samples)) return abi_fail(GSV_ERR_ARG, "hubert: workspace too small");
+    if ((reinterpret_cast<size_t>(workspace) & 15) != 0) return abi_fail(GSV_ERR_ARG, "hubert: workspace must be 16-byte aligned");
+    hipStream_t st = S(stream);
+    const HubWs w = hub_carve(c, T, static_cast<float*>(workspace));
+    const int H = c.hidden, Th = T[c.n_conv - 1], C0 = c.conv_dim[0], CL = c.conv_dim[c.n_conv - 1];
+    const int G = c.pos_groups, cg = H / G, K = c.pos_k, Tp = Th + K - 1;
+    int bad = 0;
+    // conv 0: rows of k0 samples at stride s0 over the waveform, then GroupNorm(C0, C0) over all T0 frames + GELU
+    bad |= fgemm(st, audio, c.conv_stride[0], HT(h, "feature_extractor.conv_layers.0.conv.weight"), c.conv_kernel[0], w.act[0], C0,
+                 T[0], C0, c.conv_kernel[0]);
+    const int nch = (T[0] + GN_ROWS - 1) / GN_ROWS;
+    gn_partial_kernel<<<dim3(C0 / 64, nch), 256, 0, st>>>(w.act[0], T[0], C0, w.pmean, w.pm2);
+    gn_finalize_kernel<<<(C0 + 255) / 256, 256, 0, st>>>(w.pmean, w.pm2, nch, T[0], C0, HT(h, "feature_extractor.conv_layers.0.layer_norm.weight"),
+                                                        1e-5f, w.gmean, w.gscale);
+    const long long n4 = (long long)T[0] * C0 / 4;
+    gn_apply_gelu_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(w.act[0], n4, C0, w.gmean, w.gscale,
+                                                                       HT(h, "feature_extractor.conv_layers.0.layer_norm.bias"));
+    // convs 1..: rows of k * cin values at stride s * cin over the channels-last activations, GELU epilogue
+    for (int i = 1; i < c.n_conv; ++i) {
+        const int ci = c.conv_dim[i - 1], co = c.conv_dim[i];
+        bad |= fgemm(st, w.act[(i - 1) & 1], (long long)c.conv_stride[i] * ci, h->w_conv[i], (long long)c.conv_kernel[i] * ci,
+                     w.act[i & 1], co, T[i], co, c.conv_kernel[i] * ci, nullptr, 2);
+    }
+    float* feat = w.act[(c.n_conv - 1) & 1];
+    // feature projection: LayerNorm(CL) in place, Linear CL -> H
+    bad |= ln(st, feat, feat, Th, CL, HT(h, "feature_projection.layer_norm.weight"), HT(h, "feature_projection.layer_norm.bias"), c.eps);
+    bad |= fgemm(st, feat, CL, HT(h, "feature_projection.projection.weight"), CL, w.hid, H, Th, H, CL, HT(h, "feature_projection.projection.bias"));
+    // positional conv over the group-major padded copy: tmp = hid + gelu(conv(hid) + bias), the last frame never made
+    {
+        const long long np = (long long)G * Tp * cg, n = (long long)Th * H;
+        pos_pad_group_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w.hid, Th, H, G, K, w.pg);
+        pos_conv_split_kernel<<<dim3((cg + 63) / 64, (Th + 63) / 64, G * POS_SPLIT), 256, 0, st>>>(w.pg, h->w_pos, w.part, Th, H, G, K);
+        pos_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.part, n, H, HT(h, "encoder.pos_conv_embed.conv.bias"), w.hid, w.tmp);
+    }
+    bad |= ln(st, w.tmp, w.x, Th, H, HT(h, "encoder.layer_norm.weight"), HT(h, "encoder.layer_norm.bias"), c.eps);
+    const float scale = 1.f / sqrtf(64.f);
+    for (int l = 0; l < c.n_layer; ++l) {
+        bad |= fgemm(st, w.x, H, h->w_qkv[l], H, w.qkv, 3 * H, Th, 3 * H, H, h->b_qkv[l]);
+        hubert_attn_kernel<<<dim3((Th + ATT_QB - 1) / ATT_QB, c.n_head), 128, 0, st>>>(w.qkv, 3 * H, Th, H, scale, w.att, H);
+        bad |= fgemm(st, w.att, H, HT(h, hub_layer(l, "attention.out_proj.weight")), H, w.tmp, H, Th, H, H,
+                     HT(h, hub_layer(l, "attention.out_proj.bias")), 0, w.x, H);
+        bad |= ln(st, w.tmp, w.x, Th, H, HT(h, hub_layer(l, "layer_norm.weight")), HT(h, hub_layer(l, "layer_norm.bias")), c.eps);
+        bad |= fgemm(st, w.x, H, HT(h, hub_layer(l, "feed_forward.intermediate_dense.weight")), H, w.ffn, c.ffn, Th, c.ffn, H,
+                     HT(h, hub_layer(l, "feed_forward.intermediate_dense.bias")), 2);
+        bad |= fgemm(st, w.ffn, c.ffn, HT(h, hub_layer(l, "feed_forward.output_dense.weight")), c.ffn, w.tmp, H, Th, H, c.ffn,
+                     HT(h, hub_layer(l, "feed_forward.output_dense.bias")), 0, w.x, H);
+        bad |= ln(st, w.tmp, w.x, Th, H, HT(h, hub_layer(l, "final_layer_norm.weight")), HT(h, hub_layer(l, "final_layer_norm.bias")), c.eps);
+    }
+    // [Th][H] -> ssl [H][Th]
+    transpose_kernel<<<dim3((H + 31) / 32, (Th + 31) / 32), 256, 0, st>>>(w.x, H, ssl, Th, Th, H);
+    if (bad) return abi_fail(GSV_ERR_HIP, "hubert: a forward launch failed");
     RCHK(hipGetLastError());
     return GSV_OK;
 }

@@ -30,7 +30,7 @@ struct FGemmArgs {
     const float* R; long long ldr;    // residual [M][N] or null
     int M, N, K;
     float alpha;
-    int act;                          // 0 none, 1 mish (x * tanh(softplus(x)))
+    int act;                          // 0 none, 1 mish (x * tanh(softplus(x))), 2 exact (erf) GELU
 };
 
 __device__ __forceinline__ float mish_f(float x) {
@@ -39,14 +39,16 @@ __device__ __forceinline__ float mish_f(float x) {
     return x * tanhf(sp);
 }
 
+// nn.GELU() / F.gelu default (approximate="none"): 0.5 x (1 + erf(x / sqrt 2))
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+
 // 64 x 64 output tile per block, 4 waves (2 x 2) of 32 x 32, K staged through LDS in chunks of 32.
-static __global__ __launch_bounds__(256) void fgemm_kernel(FGemmArgs a) {
-    constexpr int KC = 32, LD = KC + 1;
-    __shared__ float xs[64 * LD];
-    __shared__ float ws[64 * LD];
+constexpr int FG_KC = 32, FG_LD = FG_KC + 1;
+// the tile at rows m0, columns n0 of one GEMM (xs / ws: 64 * FG_LD floats of LDS each); 256 threads
+__device__ __forceinline__ void fgemm_tile(const FGemmArgs& a, int m0, int n0, float* xs, float* ws) {
+    constexpr int KC = FG_KC, LD = FG_LD;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid >> 1, wn = wid & 1;
-    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     const int j = lane & 31, hf = lane >> 5;
     fa16 acc;
 #pragma unroll
@@ -84,10 +86,17 @@ static __global__ __launch_bounds__(256) void fgemm_kernel(FGemmArgs a) {
         if (m < a.M) {
             float v = a.alpha * acc[q] + bn + (a.bias_m ? a.bias_m[m] : 0.f);
             if (a.act == 1) v = mish_f(v);
+            else if (a.act == 2) v = gelu_f(v);
             if (a.R) v += a.R[(long long)m * a.ldr + n];
             a.Y[(long long)m * a.ldy + n] = v;
         }
     }
+}
+
+static __global__ __launch_bounds__(256) void fgemm_kernel(FGemmArgs a) {
+    __shared__ float xs[64 * FG_LD];
+    __shared__ float ws[64 * FG_LD];
+    fgemm_tile(a, blockIdx.y * 64, blockIdx.x * 64, xs, ws);
 }
 
 // out[c][r] = in[r][c] for r < rows, c < cols  (in row stride ldi, out row stride ldo)

@@ -25,6 +25,8 @@ EXPORTS = [
     "gsv_align_workspace", "gsv_align_viterbi", "gsv_sola_workspace", "gsv_sola",
     "gsv_ref_create", "gsv_ref_destroy", "gsv_ref_load_tensor", "gsv_ref_finalize", "gsv_ref_workspace",
     "gsv_ref_spectrogram", "gsv_ref_get_ge", "gsv_ref_extract_latent",
+    "gsv_hubert_create", "gsv_hubert_destroy", "gsv_hubert_load_tensor", "gsv_hubert_finalize", "gsv_hubert_frames",
+    "gsv_hubert_workspace", "gsv_hubert_forward",
 ]
 
 
@@ -50,6 +52,15 @@ class VocConfig(ctypes.Structure):
 class RefConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in
                 ("n_fft", "hop", "spec_bins", "hidden", "n_head", "kernel", "gin", "sv_dim", "ssl_dim", "bins")]
+
+
+HUBERT_MAX_CONV = 8
+
+
+class HubertConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "n_layer", "n_head", "ffn", "n_conv")] + [
+        (n, ctypes.c_int * HUBERT_MAX_CONV) for n in ("conv_dim", "conv_kernel", "conv_stride")] + [
+        ("pos_k", ctypes.c_int), ("pos_groups", ctypes.c_int), ("eps", ctypes.c_float)]
 
 
 _LIB = None
@@ -110,6 +121,12 @@ def lib():
         "gsv_ref_spectrogram": [vp, vp, i, vp, vp, sz, vp],
         "gsv_ref_get_ge": [vp, vp, i, vp, vp, vp, sz, vp],
         "gsv_ref_extract_latent": [vp, vp, i, vp, vp, vp, sz, vp],
+        "gsv_hubert_create": [ctypes.POINTER(HubertConfig), ctypes.POINTER(vp)],
+        "gsv_hubert_destroy": [vp],
+        "gsv_hubert_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
+        "gsv_hubert_finalize": [vp, vp],
+        "gsv_hubert_frames": [vp, i],
+        "gsv_hubert_forward": [vp, vp, i, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -127,6 +144,8 @@ def lib():
     L.gsv_voc_decode_workspace.restype = sz
     L.gsv_ref_workspace.argtypes = [vp, i, i, i]
     L.gsv_ref_workspace.restype = sz
+    L.gsv_hubert_workspace.argtypes = [vp, i]
+    L.gsv_hubert_workspace.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

@@ -195,6 +195,42 @@ def get_sovits_weights(sovits_path, tts_config) -> Sovits:
     return _build_sovits(hps, weights, tts_config)
 
 
+def read_cnhubert(path):
+    """(config dict, state dict) of a Hugging Face CN-HuBERT directory (TTS.cnhubert_path = models_dir/chinese-hubert-base,
+    gsv_tts/TTS.py:111): config.json plus model.safetensors or pytorch_model.bin.  The positional conv's weight norm comes
+    back under the weight_g / weight_v names whichever of the two namings the file uses (current torch saves
+    parametrizations.weight.original0 / original1); a "hubert." prefix (a HubertFor* head's checkpoint) is dropped.
+    Configurations this build does not run are refused here (hubert.check_config).  Device-free."""
+    from .hubert import check_config
+    path = str(path)
+    cfg_path = os.path.join(path, "config.json")
+    if not os.path.isfile(cfg_path):
+        raise FileNotFoundError("CN-HuBERT: %s has no config.json (a Hugging Face chinese-hubert-base directory is expected)" % path)
+    with open(cfg_path) as f:
+        config = json.load(f)
+    config = dict(config, **check_config(config))
+    st = os.path.join(path, "model.safetensors")
+    pt = os.path.join(path, "pytorch_model.bin")
+    if os.path.isfile(st):
+        from safetensors.torch import load_file
+        raw = load_file(st)
+    elif os.path.isfile(pt):
+        raw = torch.load(pt, map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError("CN-HuBERT: %s holds neither model.safetensors nor pytorch_model.bin" % path)
+    weights = {}
+    for k, v in raw.items():
+        if k.startswith("hubert."):
+            k = k[len("hubert."):]
+        k = k.replace("conv.parametrizations.weight.original0", "conv.weight_g").replace(
+            "conv.parametrizations.weight.original1", "conv.weight_v")
+        weights[k] = v.float()
+    for k in ("encoder.pos_conv_embed.conv.weight_g", "encoder.pos_conv_embed.conv.weight_v"):
+        if k not in weights:
+            raise ValueError("CN-HuBERT: %s has no %s (a weight-normed positional conv is expected)" % (path, k))
+    return config, weights
+
+
 def convert_to_safetensors(checkpoint_path, output_dir=None) -> str:
     """TTS.to_safetensors (gsv_tts/TTS.py:1482-1523): a `.pth` SoVITS checkpoint becomes {hps.json, model.safetensors},
     a `.ckpt` GPT checkpoint {config.json, model.safetensors} -- the directory form both loaders read.  The tensors

@@ -440,3 +440,114 @@ def synth_sv_emb(i: int, seed: int = 1234) -> np.ndarray:
 def synth_ssl(i: int, n_frames: int, seed: int = 1234) -> np.ndarray:
     """CN-HuBERT last_hidden_state stand-in, channels-first [1, 768, n_frames]."""
     return (hashed_uniform("ssl%d" % i, (1, 768, n_frames), seed) * np.float32(_SQRT3)).astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------
+# CN-HuBERT (transformers HubertModel, chinese-hubert-base shapes) -- the model behind TTS._get_prompt
+# --------------------------------------------------------------------------------------
+def hubert_config(**overrides) -> dict:
+    """config.json fields of HubertConfig() (the defaults chinese-hubert-base is believed to use), with overrides."""
+    cfg = dict(model_type="hubert", hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
+               conv_dim=[512] * 7, conv_kernel=[10, 3, 3, 3, 3, 2, 2], conv_stride=[5, 2, 2, 2, 2, 2, 2],
+               num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16, feat_extract_norm="group",
+               do_stable_layer_norm=False, conv_bias=False, hidden_act="gelu", feat_extract_activation="gelu",
+               feat_proj_layer_norm=True, layer_norm_eps=1e-5)
+    cfg.update(overrides)
+    return cfg
+
+
+def hubert_spec(cfg: dict) -> "OrderedDict[str, tuple]":
+    """HubertModel state-dict names and shapes; the positional conv's weight norm under the weight_g / weight_v names."""
+    H, F, dims = cfg["hidden_size"], cfg["intermediate_size"], cfg["conv_dim"]
+    k, G = cfg["num_conv_pos_embeddings"], cfg["num_conv_pos_embedding_groups"]
+    s = OrderedDict()
+    for i, (d, ks) in enumerate(zip(dims, cfg["conv_kernel"])):
+        s["feature_extractor.conv_layers.%d.conv.weight" % i] = (d, 1 if i == 0 else dims[i - 1], ks)
+        if i == 0:
+            s["feature_extractor.conv_layers.0.layer_norm.weight"] = (d,)
+            s["feature_extractor.conv_layers.0.layer_norm.bias"] = (d,)
+    s["feature_projection.layer_norm.weight"] = (dims[-1],)
+    s["feature_projection.layer_norm.bias"] = (dims[-1],)
+    s["feature_projection.projection.weight"] = (H, dims[-1])
+    s["feature_projection.projection.bias"] = (H,)
+    s["encoder.pos_conv_embed.conv.bias"] = (H,)
+    s["encoder.pos_conv_embed.conv.weight_g"] = (1, 1, k)
+    s["encoder.pos_conv_embed.conv.weight_v"] = (H, H // G, k)
+    s["encoder.layer_norm.weight"] = (H,)
+    s["encoder.layer_norm.bias"] = (H,)
+    for l in range(cfg["num_hidden_layers"]):
+        p = "encoder.layers.%d." % l
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            s[p + "attention.%s.weight" % n] = (H, H)
+            s[p + "attention.%s.bias" % n] = (H,)
+        s[p + "layer_norm.weight"] = (H,)
+        s[p + "layer_norm.bias"] = (H,)
+        s[p + "feed_forward.intermediate_dense.weight"] = (F, H)
+        s[p + "feed_forward.intermediate_dense.bias"] = (F,)
+        s[p + "feed_forward.output_dense.weight"] = (H, F)
+        s[p + "feed_forward.output_dense.bias"] = (H,)
+        s[p + "final_layer_norm.weight"] = (H,)
+        s[p + "final_layer_norm.bias"] = (H,)
+    return s
+
+
+def hubert_weights(cfg: dict = None, seed: int = 1234) -> "OrderedDict[str, np.ndarray]":
+    """Seeded tensors for hubert_spec: He-scaled strided convs (GELU keeps the activations O(1) through the encoder), q / k
+    scaled for attention logits with a spread of a few units, and a weight-norm gain that gives the positional conv the
+    1/sqrt(fan_in) effective scale."""
+    cfg = cfg or hubert_config()
+    out = OrderedDict()
+    for name, shape in hubert_spec(cfg).items():
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        if name.endswith("weight_g"):
+            # w = g v / ||v|| over H * H/G values per tap: element scale g / sqrt(H * H/G) = 1/sqrt(H/G * k) at g = sqrt(H / k)
+            v = _std(name, shape, 0.3, seed, mean=math.sqrt(cfg["hidden_size"] / cfg["num_conv_pos_embeddings"]))
+        elif name.endswith("weight_v"):
+            v = _std(name, shape, 1.0, seed)
+        elif "norm" in name and name.endswith("weight"):
+            v = _std(name, shape, 0.1, seed, mean=1.0)
+        elif name.startswith("feature_extractor.conv_layers.") and not name.startswith("feature_extractor.conv_layers.0."):
+            v = _std(name, shape, math.sqrt(2.0 / fan_in), seed)
+        elif name.endswith(("q_proj.weight", "k_proj.weight")):
+            v = _std(name, shape, 1.5 / math.sqrt(fan_in), seed)
+        elif name.endswith("weight"):
+            v = _std(name, shape, 1.0 / math.sqrt(fan_in), seed)
+        else:
+            v = _std(name, shape, 0.1 if "norm" in name else 0.05, seed)
+        out[name] = v
+    return out
+
+
+def write_hubert_dir(path, cfg: dict = None, seed: int = 1234, naming: str = "parametrizations", fmt: str = "safetensors"):
+    """A Hugging Face directory (config.json + model.safetensors or pytorch_model.bin) holding hubert_weights(cfg, seed).
+    naming "parametrizations": the positional conv's weight norm as parametrizations.weight.original0 / original1 (what
+    current torch saves); "weight_g": the older weight_g / weight_v names."""
+    import json
+    import os
+    import torch
+    cfg = cfg or hubert_config()
+    os.makedirs(path, exist_ok=True)
+    sd = OrderedDict()
+    for name, a in hubert_weights(cfg, seed).items():
+        if naming == "parametrizations":
+            name = name.replace("conv.weight_g", "conv.parametrizations.weight.original0").replace(
+                "conv.weight_v", "conv.parametrizations.weight.original1")
+        elif naming != "weight_g":
+            raise ValueError("naming must be 'parametrizations' or 'weight_g'")
+        sd[name] = torch.from_numpy(a)
+    sd["masked_spec_embed"] = torch.from_numpy(_std("masked_spec_embed", (cfg["hidden_size"],), 1.0, seed))
+    with open(os.path.join(path, "config.json"), "w") as f:
+        json.dump(dict(cfg, architectures=["HubertModel"]), f, indent=1)
+    if fmt == "safetensors":
+        from safetensors.torch import save_file
+        save_file(dict(sd), os.path.join(path, "model.safetensors"))
+    elif fmt == "bin":
+        torch.save(dict(sd), os.path.join(path, "pytorch_model.bin"))
+    else:
+        raise ValueError("fmt must be 'safetensors' or 'bin'")
+    return path
+
+
+def synth_wav16k(i: int, seconds: float, seed: int = 1234) -> np.ndarray:
+    """A prompt waveform at 16 kHz: synth_audio's partials and noise, int(16000 * seconds) samples."""
+    return synth_audio(100 + i, int(round(16000 * seconds)), seed)

@@ -10,14 +10,16 @@ Drop-in surface kept from the reference:
     load_gpt_model / load_sovits_model / unload_* / get_*_list                 TTS.py:1264-1345
     AudioClip(audio_data, samplerate, audio_len_s, subtitles, orig_text)       Player.py:68-99
 
-What sits in front of the hot path in the reference -- G2P text frontends, audio file decoding / resampling,
-the CN-HuBERT and ERes2Net models -- is OUT OF SCOPE of this build (CPU string
-processing and third-party models whose packages are not installable here).  Their *outputs* enter through the
-same caches the reference keeps:
+CN-HuBERT runs on the device (hubert.py, loaded lazily from models_dir/chinese-hubert-base as TTS.py:111 does).  What
+else sits in front of the hot path in the reference -- G2P text frontends, audio file decoding / resampling, the
+ERes2Net and RoBERTa models -- is OUT OF SCOPE of this build (CPU string processing and
+third-party models whose packages are not installable here).  Their *outputs* enter through the same caches the
+reference keeps:
     cache_spk_audio(path, ge=...)  or  cache_spk_audio(path, audio=<waveform>, sv_emb=<ERes2Net embedding>)
                                    (spectrogram + get_ge on the device; the reference: TTS.py:1346, 1576)
-    cache_prompt_audio(path, text, prompt=... | ssl_content=<CN-HuBERT features>, phones1=..., bert1=...)
-                                   (extract_latent on the device; TTS.py:1391, 1556)
+    cache_prompt_audio(path, text, prompt=... | ssl_content=<CN-HuBERT features> | audio=<16 kHz waveform>,
+                       phones1=..., bert1=...)
+                                   (CN-HuBERT + extract_latent on the device; TTS.py:1391, 1556)
     set_text_frontend(fn)   fn(text) -> (phones2, word2ph, bert2[P,1024], norm_text)
 With those in place infer()/infer_batched()/infer_stream() behave as in the reference, including
 `return_subtitles=True`: the frame->phoneme alignment runs on the device (subtitles.viterbi_monotonic ->
@@ -154,6 +156,9 @@ class TTS:
         self.models_dir = models_dir if models_dir is not None else Path.home() / ".cache" / "gsv"
         self.default_gpt_path = Path(self.models_dir) / "s1v3.ckpt"
         self.default_sovits_path = Path(self.models_dir) / "s2Gv2ProPlus.pth"
+        self.cnhubert_path = Path(self.models_dir) / "chinese-hubert-base"
+        self.always_load_cnhubert = always_load_cnhubert
+        self.cnhubert_model = None
         self.gpt_models: dict = {}
         self.sovits_models: dict = {}
         self.spk_audio_cache: dict = {}
@@ -239,24 +244,47 @@ class TTS:
         entry["ge"][sovits_model] = ge.to(self.tts_config.device)
 
     def cache_prompt_audio(self, prompt_audio_paths, prompt_audio_texts, prompt=None, phones1=None, bert1=None,
-                           ssl_content=None, sovits_model=None):
+                           ssl_content=None, sovits_model=None, audio=None):
         """TTS.py:1391-1440.  `prompt` int64 [1, Ly], or `ssl_content` [1, 768, Th] (CN-HuBERT last_hidden_state,
-        transposed as in TTS._get_prompt): then extract_latent runs on the device."""
+        transposed as in TTS._get_prompt), or `audio`, the prompt waveform as mono fp32 at 16 kHz ([n] or [1, n]): then
+        CN-HuBERT (TTS._get_prompt: + 0.3 s of zeros) and extract_latent run on the device.  CN-HuBERT is loaded from
+        models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Resampling from
+        other rates is not part of this build: the caller brings 16 kHz audio."""
         if not prompt_audio_texts:
             raise ValueError("prompt_audio_text must not be empty")
+        if prompt is None and ssl_content is None and audio is not None:
+            ssl_content = self._cnhubert_ssl(audio)
         if prompt is None and ssl_content is not None:
             sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
             prompt = self.sovits_models[sovits_model].vq_model.extract_latent(ssl_content)[0, 0].unsqueeze(0)
         if prompt is None or phones1 is None:
-            raise NotImplementedError("CN-HuBERT and G2P are outside this build's scope; pass prompt=int64[1,Ly] or "
-                                      "ssl_content=[1,768,Th], and phones1=list[int] (and bert1=[Lx1,1024])")
+            raise NotImplementedError("decoding / resampling audio files and G2P are outside this build's scope; pass "
+                                      "prompt=int64[1,Ly], ssl_content=[1,768,Th] or audio=<mono fp32 16 kHz waveform>, and "
+                                      "phones1=list[int] (and bert1=[Lx1,1024])")
         if bert1 is None:
             bert1 = torch.zeros(len(phones1), 1024)
         self.prompt_audio_cache[prompt_audio_paths] = {
             "prompt": prompt.to(self.tts_config.device), "phones1": list(phones1),
             "bert1": bert1.to(self.tts_config.device), "text": prompt_audio_texts}
+
+    def _cnhubert_ssl(self, audio):
+        """TTS._get_prompt's ssl_content from a 16 kHz waveform, on the device (hubert.py)"""
+        from .hubert import load_cnhubert
+        try:
+            if self.cnhubert_model is None:
+                self.cnhubert_model = load_cnhubert(self.cnhubert_path, self.tts_config.device)
+            a = torch.as_tensor(audio)
+            if a.dim() == 2 and a.shape[0] == 1:
+                a = a[0]
+            if a.dim() != 1:
+                raise ValueError("audio must be one mono waveform at 16 kHz ([n] or [1, n]); resampling and channel mixing "
+                                 "are outside this build's scope; got shape %s" % (tuple(a.shape),))
+            return self.cnhubert_model.prompt_ssl(a)
+        finally:
+            if not self.always_load_cnhubert:
+                self.cnhubert_model = None
 
     def del_spk_audio(self, *spk_audio_list):
         """TTS.py:1436-1448"""

@@ -335,8 +335,8 @@ int gsv_sola(const float* prev_tail, const float* chunk, int n, int overlap, int
  *   gsv_ref_extract_latent  SynthesizerTrn.extract_latent (models.py:431-434): ssl_proj (k 2, stride 2) and the
  *                           nearest-codebook search of EuclideanCodebook.quantize (module/core_vq.py:124-128)
  * Tensors ("ref_enc.*", "sv_emb.*", "prelu.weight", "ssl_proj.*", "quantizer.vq.layers.0._codebook.embed") are
- * given under their checkpoint names, device fp32, before finalize.  Audio decoding / resampling and the CN-HuBERT
- * and ERes2Net models that produce `ssl` and `sv_emb` are outside this library. */
+ * given under their checkpoint names, device fp32, before finalize.  `ssl` comes from CN-HuBERT (gsv_hubert_* below);
+ * audio decoding / resampling and the ERes2Net model that produces `sv_emb` are outside this library. */
 typedef struct gsv_ref gsv_ref;
 typedef struct gsv_ref_config {
     int n_fft;      /* hps.data.filter_length == win_length (2048) */
@@ -366,6 +366,44 @@ int gsv_ref_get_ge(gsv_ref* h, const float* spec, int n_frames, const float* sv_
  * [n_ssl/2]; margin fp32 [n_ssl/2] or NULL = distance gap between the best and the second-best code */
 int gsv_ref_extract_latent(gsv_ref* h, const float* ssl, int n_ssl, int64_t* codes, float* margin, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/* CN-HuBERT, once per new prompt: HubertModel(wav16k)["last_hidden_state"] as TTS._get_prompt calls it
+ * (gsv_tts/TTS.py:1556-1570; GPT_SoVITS/Featurizer/cnhubert.py wraps transformers.HubertModel), fp32 in every mode.
+ * The configuration HubertConfig() describes (feat_extract_norm "group", do_stable_layer_norm False, no conv bias, exact
+ * GELU) is the only one: feature encoder (conv 0 + GroupNorm over all frames, strided convs), LayerNorm + projection,
+ * grouped positional conv with weight norm (dim 2), encoder.layer_norm, post-LN transformer layers (no mask, batch 1).
+ * Tensors under their Hugging Face state-dict names ("feature_extractor.*", "feature_projection.*", "encoder.*"), device
+ * fp32, before finalize; the positional conv's weight norm is accepted as weight_g / weight_v or as
+ * parametrizations.weight.original0 / original1 and folded at finalize.  Resampling to 16 kHz is the caller's. */
+typedef struct gsv_hubert gsv_hubert;
+#define GSV_HUBERT_MAX_CONV 8
+typedef struct gsv_hubert_config {
+    int hidden;                           /* hidden_size (768); head dim hidden / n_head must be 64 */
+    int n_layer;                          /* num_hidden_layers (12) */
+    int n_head;                           /* num_attention_heads (12) */
+    int ffn;                              /* intermediate_size (3072) */
+    int n_conv;                           /* len(conv_dim) (7) */
+    int conv_dim[GSV_HUBERT_MAX_CONV];    /* 512 each; multiples of 64, <= 1024 */
+    int conv_kernel[GSV_HUBERT_MAX_CONV]; /* 10, 3, 3, 3, 3, 2, 2 */
+    int conv_stride[GSV_HUBERT_MAX_CONV]; /* 5, 2, 2, 2, 2, 2, 2 */
+    int pos_k;                            /* num_conv_pos_embeddings (128, even) */
+    int pos_groups;                       /* num_conv_pos_embedding_groups (16) */
+    float eps;                            /* layer_norm_eps (1e-5); GroupNorm keeps torch's 1e-5 */
+} gsv_hubert_config;
+/* refuses (GSV_ERR_ARG, gsv_last_error says why) any shape the kernels do not support */
+int gsv_hubert_create(const gsv_hubert_config* cfg, gsv_hubert** out);
+int gsv_hubert_destroy(gsv_hubert* h);
+int gsv_hubert_load_tensor(gsv_hubert* h, const char* name, const float* data, int64_t numel, void* stream);
+int gsv_hubert_finalize(gsv_hubert* h, void* stream);
+/* output frames Th for n_samples: T0 = (n - k0) / s0 + 1, Ti = (T(i-1) - ki) / si + 1; 0 when the input is too short
+ * (fewer than 400 samples for the default shapes) */
+int gsv_hubert_frames(gsv_hubert* h, int n_samples);
+/* device bytes of the caller-owned workspace of one forward over n_samples; 0 when n_samples is too short */
+size_t gsv_hubert_workspace(gsv_hubert* h, int n_samples);
+/* audio fp32 [n_samples] (mono, 16 kHz, as the model reads it: no normalisation) -> ssl fp32 [hidden][Th] channels-first
+ * (last_hidden_state transposed, what gsv_ref_extract_latent takes).  Nothing is allocated. */
+int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* ssl, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }
