@@ -1,5 +1,6 @@
-// C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section; kernels in refaudio.h) and of
-// CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm).
+// C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section; kernels in refaudio.h), of
+// CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm) and of ERes2NetV2 with its resampler and
+// fbank (gsv_sv_*; kernels in sv.h, which uses the same fgemm for the DFT and the mel filter bank).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "gsv_error.h"
 #include "hubert.h"
 #include "refaudio.h"
+#include "sv.h"
 
 using namespace gsv;
 
@@ -545,6 +547,456 @@ int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* 
     if (bad) return abi_fail(GSV_ERR_HIP, "hubert: a forward launch failed");
     RCHK(hipGetLastError());
     return GSV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// ERes2NetV2 (speaker verification): resample, fbank, forward3
+// ------------------------------------------------------------------------------------------------------------------
+struct gsv_sv {
+    gsv_sv_config cfg;
+    std::map<std::string, std::pair<float*, int64_t>> t;   // loaded tensors (device, fp32)
+    bool finalized = false;
+    struct Conv { float* w; float* b; int cout, cin, k; };
+    std::map<std::string, Conv> conv;                       // BN-folded, [cout][k][k][cin], keyed by the conv's name
+    float* dft = nullptr;                                   // [2 * 257][512]
+    float* mel = nullptr;                                   // [80][257]
+    std::vector<void*> owned;
+};
+
+namespace {
+
+int sv_alloc(gsv_sv* h, float** p, size_t floats) {
+    RCHK(hipMalloc(reinterpret_cast<void**>(p), floats * sizeof(float)));
+    h->owned.push_back(*p);
+    return GSV_OK;
+}
+
+int gcd_i(int a, int b) { while (b) { const int r = a % b; a = b; b = r; } return a; }
+
+// gcd-reduced rates and the kernel half-width of torchaudio's sinc resampler; false on bad rates
+bool rs_params(int orig, int nw, int* o, int* n, int* width) {
+    if (orig < 1 || nw < 1) return false;
+    const int g = gcd_i(orig, nw);
+    *o = orig / g;
+    *n = nw / g;
+    *width = (int)std::ceil(6.0 * *o / ((double)std::min(*o, *n) * 0.99));
+    return (long long)*n * (2 * *width + *o) <= (1LL << 24);
+}
+
+long long rs_length(long long n, int orig, int nw) {
+    int o, w, width;
+    if (n < 0 || !rs_params(orig, nw, &o, &w, &width)) return -1;
+    if (o == w) return n;
+    return (w * n + o - 1) / o;
+}
+
+int fb_frames(long long n16) { return n16 < FB_WIN ? 0 : (int)(1 + (n16 - FB_WIN) / FB_HOP); }
+
+// stage geometry: frequency rows F[s], frames T[s] (stage 0 stride 1, stages 1-3 stride 2 in both axes)
+struct SvGeo { int F[4], T[4]; };
+SvGeo sv_geo(const gsv_sv_config& c, int T) {
+    SvGeo g;
+    int f = c.feat_dim, t = T;
+    for (int s = 0; s < 4; ++s) {
+        if (s > 0) { f = (f + 1) / 2; t = (t + 1) / 2; }
+        g.F[s] = f;
+        g.T[s] = t;
+    }
+    return g;
+}
+
+// workspace of one embed: resample table and output, fbank buffers, then the model's zero-padded activations
+struct SvWs {
+    float *tab, *y16, *fr, *Z, *P, *E, *feat;
+    float *model;                          // start of the zero-filled model region
+    float *in0, *stem;
+    float *x[4][2], *c1[4], *cat[4], *hh[4], *fu[4];
+    float *ds, *h34, *fuse;
+    size_t model_floats, total;
+};
+SvWs sv_carve(const gsv_sv_config& c, long long n, int sr, float* base) {
+    SvWs w;
+    size_t off = 0;
+    auto take = [&](size_t k) { float* r = base ? base + off : nullptr; off += up(k); return r; };
+    int o = 1, nw = 1, width = 0;
+    rs_params(sr, 16000, &o, &nw, &width);
+    const long long n16 = rs_length(n, sr, 16000);
+    const int T = fb_frames(n16);
+    w.tab = take(o == nw ? 0 : (size_t)nw * (2 * width + o));
+    w.y16 = take(sr == 16000 ? 0 : (size_t)n16);
+    w.fr = take((size_t)T * FB_NFFT);
+    w.Z = take((size_t)T * 2 * FB_BINS);
+    w.P = take((size_t)T * FB_BINS);
+    w.E = take((size_t)T * FB_MELS);
+    w.feat = take((size_t)T * FB_MELS);
+    const size_t m0 = off;
+    w.model = base ? base + off : nullptr;
+    const SvGeo g = sv_geo(c, T);
+    const int m = c.m_channels;
+    auto pix = [](int F, int Tt) { return (size_t)(F + 2) * (Tt + 2); };
+    w.in0 = take(pix(c.feat_dim, T));
+    w.stem = take(pix(c.feat_dim, T) * m);
+    for (int s = 0; s < 4; ++s) {
+        const size_t p = pix(g.F[s], g.T[s]);
+        const int C = 4 * (m << s), wd = c.width[s];
+        w.x[s][0] = take(p * C);
+        w.x[s][1] = take(p * C);
+        w.c1[s] = take(p * 4 * wd);
+        w.cat[s] = take(p * 4 * wd);
+        w.hh[s] = s >= 2 ? take(p * (wd / 4)) : nullptr;
+        w.fu[s] = s >= 2 ? take(p * wd) : nullptr;
+    }
+    const size_t p4 = pix(g.F[3], g.T[3]);
+    w.ds = take(p4 * 32 * m);
+    w.h34 = take(p4 * 8 * m);
+    w.fuse = take(p4 * 32 * m);
+    w.model_floats = off - m0;
+    w.total = off;
+    return w;
+}
+
+std::string sv_blk(int s, int b, const char* rest) {
+    return "layer" + std::to_string(s + 1) + "." + std::to_string(b) + "." + rest;
+}
+
+// every conv forward3 runs: (conv name, weight, BN prefix or "", conv bias or "", cout, cin, k)
+struct SvConvSpec { std::string key, weight, bn, bias; int cout, cin, k; };
+std::vector<SvConvSpec> sv_specs(const gsv_sv_config& c) {
+    std::vector<SvConvSpec> v;
+    const int m = c.m_channels;
+    v.push_back({"conv1", "conv1.weight", "bn1.", "", m, 1, 3});
+    int in = m;
+    for (int s = 0; s < 4; ++s) {
+        const int P = m << s, C = 4 * P, wd = c.width[s];
+        for (int b = 0; b < c.blocks[s]; ++b) {
+            const int stride = (b == 0 && s > 0) ? 2 : 1;
+            v.push_back({sv_blk(s, b, "conv1"), sv_blk(s, b, "conv1.weight"), sv_blk(s, b, "bn1."), "", 4 * wd, in, 1});
+            for (int i = 0; i < 4; ++i) {
+                const std::string ci = "convs." + std::to_string(i), bi = "bns." + std::to_string(i) + ".";
+                v.push_back({sv_blk(s, b, ci.c_str()), sv_blk(s, b, (ci + ".weight").c_str()), sv_blk(s, b, bi.c_str()), "", wd, wd, 3});
+            }
+            if (s >= 2)
+                for (int j = 0; j < 3; ++j) {
+                    const std::string f = "fuse_models." + std::to_string(j) + ".local_att.";
+                    v.push_back({sv_blk(s, b, (f + "0").c_str()), sv_blk(s, b, (f + "0.weight").c_str()), sv_blk(s, b, (f + "1.").c_str()),
+                                 sv_blk(s, b, (f + "0.bias").c_str()), wd / 4, 2 * wd, 1});
+                    v.push_back({sv_blk(s, b, (f + "3").c_str()), sv_blk(s, b, (f + "3.weight").c_str()), sv_blk(s, b, (f + "4.").c_str()),
+                                 sv_blk(s, b, (f + "3.bias").c_str()), wd, wd / 4, 1});
+                }
+            v.push_back({sv_blk(s, b, "conv3"), sv_blk(s, b, "conv3.weight"), sv_blk(s, b, "bn3."), "", C, 4 * wd, 1});
+            if (stride != 1 || in != C)
+                v.push_back({sv_blk(s, b, "shortcut"), sv_blk(s, b, "shortcut.0.weight"), sv_blk(s, b, "shortcut.1."), "", C, in, 1});
+            in = C;
+        }
+    }
+    v.push_back({"layer3_ds", "layer3_ds.weight", "", "", 32 * m, 16 * m, 3});
+    v.push_back({"fuse34.0", "fuse34.local_att.0.weight", "fuse34.local_att.1.", "fuse34.local_att.0.bias", 8 * m, 64 * m, 1});
+    v.push_back({"fuse34.3", "fuse34.local_att.3.weight", "fuse34.local_att.4.", "fuse34.local_att.3.bias", 32 * m, 8 * m, 1});
+    return v;
+}
+
+// one conv over padded channels-last buffers: input geometry (Fi, Ti), output (Fi - 1) / s + 1 x (Ti - 1) / s + 1
+struct SvIO {
+    const float* x1; const float* x2; int src, ldx;
+    float* y; int ldy;
+    const float* r = nullptr; int ldr = 0;
+    const float* a = nullptr; int lda = 0; const float* b = nullptr; int ldb = 0;
+};
+int sv_conv(hipStream_t st, const gsv_sv::Conv& cw, int stride, int Fi, int Ti, const SvIO& io, int act) {
+    SvConvArgs a;
+    a.X1 = io.x1; a.X2 = io.x2; a.src = io.src; a.ldx = io.ldx; a.Tpi = Ti + 2;
+    a.Cin = io.src == SV_SRC_CAT ? cw.cin / 2 : cw.cin;
+    a.k = cw.k; a.s = stride; a.W = cw.w; a.bias = cw.b;
+    a.Y = io.y; a.ldy = io.ldy;
+    a.Fo = (Fi - 1) / stride + 1; a.To = (Ti - 1) / stride + 1; a.N = cw.cout;
+    a.R = io.r; a.ldr = io.ldr; a.A = io.a; a.lda = io.lda; a.B = io.b; a.ldb = io.ldb; a.act = act;
+    const long long M = (long long)a.Fo * a.To;
+    if (a.N <= 32)
+        sv_conv_kernel<4, 1><<<dim3((a.N + 31) / 32, (unsigned)((M + 127) / 128)), 256, 0, st>>>(a);
+    else
+        sv_conv_kernel<2, 2><<<dim3((a.N + 63) / 64, (unsigned)((M + 63) / 64)), 256, 0, st>>>(a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int sv_resample_run(hipStream_t st, const float* x, int n, int orig, int nw_sr, float* y, float* tab) {
+    int o, nw, width;
+    rs_params(orig, nw_sr, &o, &nw, &width);
+    if (o == nw) {
+        if (n > 0) RCHK(hipMemcpyAsync(y, x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return GSV_OK;
+    }
+    const int L = 2 * width + o;
+    const long long n_out = rs_length(n, orig, nw_sr);
+    sv_resample_table_kernel<<<(nw * L + 255) / 256, 256, 0, st>>>(tab, o, nw, width);
+    if (n_out > 0) sv_resample_kernel<<<(unsigned)((n_out + 255) / 256), 256, 0, st>>>(x, n, tab, o, nw, width, y, (int)n_out);
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int sv_fbank_run(gsv_sv* h, hipStream_t st, const float* x16, int T, float* feat, const SvWs& w) {
+    sv_frames_kernel<<<T, 256, 0, st>>>(x16, w.fr);
+    int bad = fgemm(st, w.fr, FB_NFFT, h->dft, FB_NFFT, w.Z, 2 * FB_BINS, T, 2 * FB_BINS, FB_NFFT);
+    const long long np = (long long)T * FB_BINS, ne = (long long)T * FB_MELS;
+    sv_power_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w.Z, T, w.P);
+    bad |= fgemm(st, w.P, FB_BINS, h->mel, FB_BINS, w.E, FB_MELS, T, FB_MELS, FB_BINS);
+    sv_log_kernel<<<(unsigned)((ne + 255) / 256), 256, 0, st>>>(w.E, ne, feat);
+    if (bad) return abi_fail(GSV_ERR_HIP, "sv: an fbank launch failed");
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int sv_forward_run(gsv_sv* h, hipStream_t st, const float* feat, int T, float* emb, const SvWs& w) {
+    const gsv_sv_config& c = h->cfg;
+    const SvGeo g = sv_geo(c, T);
+    const int m = c.m_channels, F = c.feat_dim;
+    auto CW = [&](const std::string& k) -> const gsv_sv::Conv& { return h->conv.at(k); };
+    RCHK(hipMemsetAsync(w.model, 0, w.model_floats * sizeof(float), st));
+    const long long nf = (long long)T * F;
+    sv_feat_pad_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, st>>>(feat, T, F, w.in0);
+    int bad = 0;
+    {
+        SvIO io{w.in0, nullptr, SV_SRC_ONE, 1, w.stem, m};
+        bad |= sv_conv(st, CW("conv1"), 1, F, T, io, SV_ACT_RELU);   // F.relu(bn1(conv1(x)))
+    }
+    const float* prev = w.stem;
+    int in = m, Fi = F, Ti = T;
+    for (int s = 0; s < 4; ++s) {
+        const int C = 4 * (m << s), wd = c.width[s], W4 = 4 * wd;
+        const int Fo = g.F[s], To = g.T[s];
+        for (int b = 0; b < c.blocks[s]; ++b) {
+            const int stride = (b == 0 && s > 0) ? 2 : 1;
+            const float* X = b == 0 ? prev : w.x[s][(b - 1) & 1];
+            const int fi = b == 0 ? Fi : Fo, ti = b == 0 ? Ti : To;
+            float* Y = w.x[s][b & 1];
+            SvIO i1{X, nullptr, SV_SRC_ONE, in, w.c1[s], W4};
+            bad |= sv_conv(st, CW(sv_blk(s, b, "conv1")), stride, fi, ti, i1, SV_ACT_HTANH);
+            const float* R = X;
+            if (stride != 1 || in != C) {
+                SvIO isc{X, nullptr, SV_SRC_ONE, in, w.x[s][1], C};   // block 0 only: its output is x[s][0]
+                bad |= sv_conv(st, CW(sv_blk(s, b, "shortcut")), stride, fi, ti, isc, SV_ACT_NONE);
+                R = w.x[s][1];
+            }
+            for (int i = 0; i < 4; ++i) {
+                SvIO ic{w.c1[s], nullptr, SV_SRC_ONE, W4, w.cat[s] + i * wd, W4};
+                if (i > 0 && s < 2) {            // sp = sp + spx[i]
+                    ic.x1 = w.cat[s] + (i - 1) * wd;
+                    ic.x2 = w.c1[s] + i * wd;
+                    ic.src = SV_SRC_ADD;
+                } else if (i > 0) {              // sp = AFF(sp, spx[i])
+                    const std::string f = "fuse_models." + std::to_string(i - 1) + ".local_att.";
+                    SvIO ih{w.cat[s] + (i - 1) * wd, w.c1[s] + i * wd, SV_SRC_CAT, W4, w.hh[s], wd / 4};
+                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "0").c_str())), 1, Fo, To, ih, SV_ACT_SILU);
+                    SvIO ia{w.hh[s], nullptr, SV_SRC_ONE, wd / 4, w.fu[s], wd};
+                    ia.a = w.cat[s] + (i - 1) * wd; ia.lda = W4;
+                    ia.b = w.c1[s] + i * wd; ia.ldb = W4;
+                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "3").c_str())), 1, Fo, To, ia, SV_ACT_AFF);
+                    ic.x1 = w.fu[s];
+                    ic.ldx = wd;
+                } else {
+                    ic.x1 = w.c1[s];
+                }
+                bad |= sv_conv(st, CW(sv_blk(s, b, ("convs." + std::to_string(i)).c_str())), 1, Fo, To, ic, SV_ACT_HTANH);
+            }
+            SvIO i3{w.cat[s], nullptr, SV_SRC_ONE, W4, Y, C};
+            i3.r = R;
+            i3.ldr = C;
+            bad |= sv_conv(st, CW(sv_blk(s, b, "conv3")), 1, Fo, To, i3, SV_ACT_HTANH);
+            in = C;
+        }
+        prev = w.x[s][(c.blocks[s] - 1) & 1];
+        Fi = Fo;
+        Ti = To;
+    }
+    const float* out3 = w.x[2][(c.blocks[2] - 1) & 1];
+    const float* out4 = prev;
+    const int C4 = 32 * m;
+    {
+        SvIO ids{out3, nullptr, SV_SRC_ONE, 16 * m, w.ds, C4};
+        bad |= sv_conv(st, CW("layer3_ds"), 2, g.F[2], g.T[2], ids, SV_ACT_NONE);
+        SvIO ih{out4, w.ds, SV_SRC_CAT, C4, w.h34, 8 * m};
+        bad |= sv_conv(st, CW("fuse34.0"), 1, g.F[3], g.T[3], ih, SV_ACT_SILU);
+        SvIO ia{w.h34, nullptr, SV_SRC_ONE, 8 * m, w.fuse, C4};
+        ia.a = out4; ia.lda = C4; ia.b = w.ds; ia.ldb = C4;
+        bad |= sv_conv(st, CW("fuse34.3"), 1, g.F[3], g.T[3], ia, SV_ACT_AFF);
+    }
+    sv_mean_kernel<<<(g.F[3] * C4 + 255) / 256, 256, 0, st>>>(w.fuse, g.F[3], g.T[3], C4, emb);
+    if (bad) return abi_fail(GSV_ERR_HIP, "sv: a forward launch failed");
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int sv_check_ws(gsv_sv* h, long long n, int sr, void* ws, size_t bytes) {
+    if (!h->finalized) return abi_fail(GSV_ERR_STATE, "sv: not finalized");
+    if (!ws) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (bytes < sizeof(float) * sv_carve(h->cfg, n, sr, nullptr).total) return abi_fail(GSV_ERR_ARG, "sv: workspace too small");
+    if ((reinterpret_cast<size_t>(ws) & 15) != 0) return abi_fail(GSV_ERR_ARG, "sv: workspace must be 16-byte aligned");
+    return GSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsv_sv_create(const gsv_sv_config* cfg, gsv_sv** out) {
+    if (!cfg || !out) return abi_fail(GSV_ERR_ARG, "null argument");
+    const gsv_sv_config& c = *cfg;
+    if (c.scale != 4) return abi_fail(GSV_ERR_ARG, "sv: scale %d unsupported (ERes2NetV2 with scale 4 only)", c.scale);
+    if (c.expansion != 4) return abi_fail(GSV_ERR_ARG, "sv: expansion %d unsupported (4 only)", c.expansion);
+    if (c.feat_dim != 80) return abi_fail(GSV_ERR_ARG, "sv: feat_dim %d unsupported (80-bin fbank only)", c.feat_dim);
+    if (c.m_channels < 1 || c.m_channels > 1024) return abi_fail(GSV_ERR_ARG, "sv: m_channels %d unsupported", c.m_channels);
+    for (int s = 0; s < 4; ++s) {
+        if (c.blocks[s] < 1 || c.blocks[s] > 64) return abi_fail(GSV_ERR_ARG, "sv: %d blocks in stage %d unsupported", c.blocks[s], s + 1);
+        if (c.width[s] < 4 || c.width[s] > (c.m_channels << s) * 4)
+            return abi_fail(GSV_ERR_ARG, "sv: split width %d in stage %d unsupported (4 .. 4 * planes)", c.width[s], s + 1);
+    }
+    gsv_sv* h = new gsv_sv();
+    h->cfg = c;
+    *out = h;
+    return GSV_OK;
+}
+
+int gsv_sv_destroy(gsv_sv* h) {
+    if (!h) return GSV_OK;
+    for (auto& kv : h->t) (void)hipFree(kv.second.first);
+    for (void* p : h->owned) (void)hipFree(p);
+    delete h;
+    return GSV_OK;
+}
+
+int gsv_sv_load_tensor(gsv_sv* h, const char* name, const float* data, int64_t numel, void* stream) {
+    if (!h || !name || !data || numel < 1) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return abi_fail(GSV_ERR_STATE, "sv: load after finalize");
+    const std::string n(name);
+    bool known = false;
+    for (const char* p : {"conv1.", "bn1.", "layer1.", "layer2.", "layer3.", "layer4.", "layer3_ds.", "fuse34."})
+        known |= n.rfind(p, 0) == 0;
+    if (!known || n.find("num_batches_tracked") != std::string::npos) return abi_fail(GSV_ERR_ARG, "sv: unknown tensor %s", name);
+    float* d = nullptr;
+    RCHK(hipMalloc(reinterpret_cast<void**>(&d), numel * sizeof(float)));
+    RCHK(hipMemcpyAsync(d, data, numel * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+    auto it = h->t.find(n);
+    if (it != h->t.end()) (void)hipFree(it->second.first);
+    h->t[n] = {d, numel};
+    return GSV_OK;
+}
+
+int gsv_sv_finalize(gsv_sv* h, void* stream) {
+    if (!h) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return GSV_OK;
+    hipStream_t st = S(stream);
+    const std::vector<SvConvSpec> specs = sv_specs(h->cfg);
+    auto need = [&](const std::string& n, int64_t numel) -> int {
+        auto it = h->t.find(n);
+        if (it == h->t.end()) return abi_fail(GSV_ERR_STATE, "sv: tensor %s was not loaded", n.c_str());
+        if (it->second.second != numel)
+            return abi_fail(GSV_ERR_ARG, "sv: tensor %s has %lld elements, expected %lld", n.c_str(), (long long)it->second.second,
+                            (long long)numel);
+        return GSV_OK;
+    };
+    int rc;
+    for (const auto& sp : specs) {
+        if ((rc = need(sp.weight, (int64_t)sp.cout * sp.cin * sp.k * sp.k))) return rc;
+        if (!sp.bn.empty())
+            for (const char* f : {"weight", "bias", "running_mean", "running_var"})
+                if ((rc = need(sp.bn + f, sp.cout))) return rc;
+        if (!sp.bias.empty() && (rc = need(sp.bias, sp.cout))) return rc;
+    }
+    for (const auto& sp : specs) {
+        gsv_sv::Conv cv{nullptr, nullptr, sp.cout, sp.cin, sp.k};
+        const long long nw = (long long)sp.cout * sp.cin * sp.k * sp.k;
+        if ((rc = sv_alloc(h, &cv.w, nw)) || (rc = sv_alloc(h, &cv.b, sp.cout))) return rc;
+        auto T = [&](const std::string& n) -> const float* { return h->t.at(n).first; };
+        const bool bn = !sp.bn.empty();
+        sv_fold_kernel<<<(unsigned)((nw + 255) / 256), 256, 0, st>>>(
+            T(sp.weight), sp.cout, sp.cin, sp.k * sp.k, bn ? T(sp.bn + "weight") : nullptr, bn ? T(sp.bn + "bias") : nullptr,
+            bn ? T(sp.bn + "running_mean") : nullptr, bn ? T(sp.bn + "running_var") : nullptr,
+            sp.bias.empty() ? nullptr : T(sp.bias), 1e-5f, cv.w, cv.b);
+        h->conv[sp.key] = cv;
+    }
+    if ((rc = sv_alloc(h, &h->dft, (size_t)2 * FB_BINS * FB_NFFT)) || (rc = sv_alloc(h, &h->mel, (size_t)FB_MELS * FB_BINS))) return rc;
+    sv_dft_kernel<<<(FB_BINS * FB_NFFT + 255) / 256, 256, 0, st>>>(h->dft);
+    sv_mel_kernel<<<(FB_MELS * FB_BINS + 255) / 256, 256, 0, st>>>(h->mel);
+    RCHK(hipGetLastError());
+    // the folded copies are all forward3 reads: the loaded originals go once the folds have run
+    RCHK(hipStreamSynchronize(st));
+    for (auto& kv : h->t) (void)hipFree(kv.second.first);
+    h->t.clear();
+    h->finalized = true;
+    return GSV_OK;
+}
+
+int gsv_sv_resample_length(int n_samples, int orig_sr, int new_sr) {
+    const long long r = rs_length(n_samples, orig_sr, new_sr);
+    return (r < 0 || r > 0x7fffffff) ? 0 : (int)r;
+}
+
+size_t gsv_sv_resample_workspace(int orig_sr, int new_sr) {
+    int o, nw, width;
+    if (!rs_params(orig_sr, new_sr, &o, &nw, &width)) return 0;
+    return sizeof(float) * up((size_t)nw * (2 * width + o));
+}
+
+int gsv_sv_resample(const float* x, int n_samples, int orig_sr, int new_sr, float* y, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    int o, nw, width;
+    if (!x || !y || n_samples < 1) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (!rs_params(orig_sr, new_sr, &o, &nw, &width)) return abi_fail(GSV_ERR_ARG, "sv: resampling %d -> %d Hz unsupported", orig_sr, new_sr);
+    if (o != nw && (!workspace || workspace_bytes < gsv_sv_resample_workspace(orig_sr, new_sr)))
+        return abi_fail(GSV_ERR_ARG, "sv: resample workspace too small");
+    return sv_resample_run(S(stream), x, n_samples, orig_sr, new_sr, y, static_cast<float*>(workspace));
+}
+
+int gsv_sv_frames(gsv_sv* h, int n_samples, int sample_rate) {
+    if (!h) return 0;
+    const long long n16 = rs_length(n_samples, sample_rate, 16000);
+    return n16 < 0 ? 0 : fb_frames(n16);
+}
+
+size_t gsv_sv_workspace(gsv_sv* h, int n_samples, int sample_rate) {
+    if (!h || gsv_sv_frames(h, n_samples, sample_rate) < 1) return 0;
+    return sizeof(float) * sv_carve(h->cfg, n_samples, sample_rate, nullptr).total;
+}
+
+int gsv_sv_fbank(gsv_sv* h, const float* wav16k, int n_samples, float* feat, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !wav16k || !feat) return abi_fail(GSV_ERR_ARG, "null argument");
+    const int T = fb_frames(n_samples);
+    if (T < 1) return abi_fail(GSV_ERR_ARG, "sv: %d samples are too short for one fbank frame (400)", n_samples);
+    int rc;
+    if ((rc = sv_check_ws(h, n_samples, 16000, workspace, workspace_bytes))) return rc;
+    const SvWs w = sv_carve(h->cfg, n_samples, 16000, static_cast<float*>(workspace));
+    return sv_fbank_run(h, S(stream), wav16k, T, feat, w);
+}
+
+int gsv_sv_forward(gsv_sv* h, const float* feat, int n_frames, float* sv_emb, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !feat || !sv_emb) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (n_frames < 1 || n_frames > (0x7fffffff - FB_WIN) / FB_HOP) return abi_fail(GSV_ERR_ARG, "sv: %d frames", n_frames);
+    const long long n16 = FB_WIN + (long long)FB_HOP * (n_frames - 1);
+    int rc;
+    if ((rc = sv_check_ws(h, n16, 16000, workspace, workspace_bytes))) return rc;
+    const SvWs w = sv_carve(h->cfg, n16, 16000, static_cast<float*>(workspace));
+    return sv_forward_run(h, S(stream), feat, n_frames, sv_emb, w);
+}
+
+int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, float* sv_emb, void* workspace, size_t workspace_bytes,
+                 void* stream) {
+    if (!h || !wav || !sv_emb) return abi_fail(GSV_ERR_ARG, "null argument");
+    int o, nw, width;
+    if (!rs_params(sample_rate, 16000, &o, &nw, &width)) return abi_fail(GSV_ERR_ARG, "sv: sample rate %d unsupported", sample_rate);
+    const int T = gsv_sv_frames(h, n_samples, sample_rate);
+    if (T < 1) return abi_fail(GSV_ERR_ARG, "sv: %d samples at %d Hz are too short for one fbank frame", n_samples, sample_rate);
+    int rc;
+    if ((rc = sv_check_ws(h, n_samples, sample_rate, workspace, workspace_bytes))) return rc;
+    hipStream_t st = S(stream);
+    const SvWs w = sv_carve(h->cfg, n_samples, sample_rate, static_cast<float*>(workspace));
+    const float* x16 = wav;
+    if (sample_rate != 16000) {
+        if ((rc = sv_resample_run(st, wav, n_samples, sample_rate, 16000, w.y16, w.tab))) return rc;
+        x16 = w.y16;
+    }
+    if ((rc = sv_fbank_run(h, st, x16, T, w.feat, w))) return rc;
+    return sv_forward_run(h, st, w.feat, T, sv_emb, w);
 }
 
 }  // extern "C"

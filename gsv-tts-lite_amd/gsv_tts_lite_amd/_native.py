@@ -27,6 +27,9 @@ EXPORTS = [
     "gsv_ref_spectrogram", "gsv_ref_get_ge", "gsv_ref_extract_latent",
     "gsv_hubert_create", "gsv_hubert_destroy", "gsv_hubert_load_tensor", "gsv_hubert_finalize", "gsv_hubert_frames",
     "gsv_hubert_workspace", "gsv_hubert_forward",
+    "gsv_sv_create", "gsv_sv_destroy", "gsv_sv_load_tensor", "gsv_sv_finalize", "gsv_sv_resample_length",
+    "gsv_sv_resample_workspace", "gsv_sv_resample", "gsv_sv_frames", "gsv_sv_workspace", "gsv_sv_fbank", "gsv_sv_forward",
+    "gsv_sv_embed",
 ]
 
 
@@ -61,6 +64,11 @@ class HubertConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("hidden", "n_layer", "n_head", "ffn", "n_conv")] + [
         (n, ctypes.c_int * HUBERT_MAX_CONV) for n in ("conv_dim", "conv_kernel", "conv_stride")] + [
         ("pos_k", ctypes.c_int), ("pos_groups", ctypes.c_int), ("eps", ctypes.c_float)]
+
+
+class SvConfig(ctypes.Structure):
+    _fields_ = [("m_channels", ctypes.c_int), ("blocks", ctypes.c_int * 4), ("width", ctypes.c_int * 4),
+                ("scale", ctypes.c_int), ("expansion", ctypes.c_int), ("feat_dim", ctypes.c_int)]
 
 
 _LIB = None
@@ -127,6 +135,16 @@ def lib():
         "gsv_hubert_finalize": [vp, vp],
         "gsv_hubert_frames": [vp, i],
         "gsv_hubert_forward": [vp, vp, i, vp, vp, sz, vp],
+        "gsv_sv_create": [ctypes.POINTER(SvConfig), ctypes.POINTER(vp)],
+        "gsv_sv_destroy": [vp],
+        "gsv_sv_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
+        "gsv_sv_finalize": [vp, vp],
+        "gsv_sv_resample_length": [i, i, i],
+        "gsv_sv_resample": [vp, i, i, i, vp, vp, sz, vp],
+        "gsv_sv_frames": [vp, i, i],
+        "gsv_sv_fbank": [vp, vp, i, vp, vp, sz, vp],
+        "gsv_sv_forward": [vp, vp, i, vp, vp, sz, vp],
+        "gsv_sv_embed": [vp, vp, i, i, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -146,6 +164,10 @@ def lib():
     L.gsv_ref_workspace.restype = sz
     L.gsv_hubert_workspace.argtypes = [vp, i]
     L.gsv_hubert_workspace.restype = sz
+    L.gsv_sv_resample_workspace.argtypes = [i, i]
+    L.gsv_sv_resample_workspace.restype = sz
+    L.gsv_sv_workspace.argtypes = [vp, i, i]
+    L.gsv_sv_workspace.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

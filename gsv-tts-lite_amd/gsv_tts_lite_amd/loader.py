@@ -231,6 +231,26 @@ def read_cnhubert(path):
     return config, weights
 
 
+def read_sv(path):
+    """The ERes2NetV2 state dict of a speaker-verification checkpoint (TTS.sv_path =
+    models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, gsv_tts/TTS.py:113; SV/sv.py loads it with torch.load): a torch file
+    holding one flat {name: tensor} mapping, read with weights_only=True.  Anything else -- another container, non-tensor
+    values, no stem conv -- is refused, as is a configuration this build does not run (sv.infer_config).  Device-free."""
+    from .sv import infer_config
+    path = str(path)
+    if not os.path.isfile(path):
+        raise FileNotFoundError("ERes2NetV2: no checkpoint at %s" % path)
+    try:
+        raw = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as e:
+        raise ValueError("ERes2NetV2: %s is not a torch state dict loadable with weights_only=True (%s)" % (path, e)) from None
+    if not isinstance(raw, dict) or not raw or not all(isinstance(k, str) and torch.is_tensor(v) for k, v in raw.items()):
+        raise ValueError("ERes2NetV2: %s does not hold a flat {name: tensor} state dict" % path)
+    weights = {k: v.float() for k, v in raw.items() if not k.endswith("num_batches_tracked")}
+    infer_config(weights)
+    return weights
+
+
 def convert_to_safetensors(checkpoint_path, output_dir=None) -> str:
     """TTS.to_safetensors (gsv_tts/TTS.py:1482-1523): a `.pth` SoVITS checkpoint becomes {hps.json, model.safetensors},
     a `.ckpt` GPT checkpoint {config.json, model.safetensors} -- the directory form both loaders read.  The tensors

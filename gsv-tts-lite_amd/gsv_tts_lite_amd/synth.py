@@ -551,3 +551,107 @@ def write_hubert_dir(path, cfg: dict = None, seed: int = 1234, naming: str = "pa
 def synth_wav16k(i: int, seconds: float, seed: int = 1234) -> np.ndarray:
     """A prompt waveform at 16 kHz: synth_audio's partials and noise, int(16000 * seconds) samples."""
     return synth_audio(100 + i, int(round(16000 * seconds)), seed)
+
+
+# --------------------------------------------------------------------------------------
+# ERes2NetV2 (speaker verification, SV/ERes2NetV2.py) -- the model behind sv_emb for v2Pro / v2ProPlus
+# --------------------------------------------------------------------------------------
+def sv_spec(m_channels: int = 64, blocks=(3, 4, 6, 3), base_width: int = 24, scale: int = 4, expansion: int = 4,
+            feat_dim: int = 80, embedding_size: int = 192) -> "OrderedDict[str, tuple]":
+    """ERes2NetV2(baseWidth, scale, expansion, m_channels) state-dict names and shapes in module order, without the BN
+    num_batches_tracked counters.  seg_1 (the embedding head forward3 does not use) is included."""
+    s = OrderedDict()
+
+    def bn(p, c):
+        for f in ("weight", "bias", "running_mean", "running_var"):
+            s[p + f] = (c,)
+
+    def aff(p, c):
+        s[p + "local_att.0.weight"] = (c // 4, 2 * c, 1, 1)
+        s[p + "local_att.0.bias"] = (c // 4,)
+        bn(p + "local_att.1.", c // 4)
+        s[p + "local_att.3.weight"] = (c, c // 4, 1, 1)
+        s[p + "local_att.3.bias"] = (c,)
+        bn(p + "local_att.4.", c)
+
+    m = m_channels
+    s["conv1.weight"] = (m, 1, 3, 3)
+    bn("bn1.", m)
+    inp = m
+    for st in range(4):
+        planes = m << st
+        w = int(math.floor(planes * (base_width / 64.0)))
+        for b in range(blocks[st]):
+            p = "layer%d.%d." % (st + 1, b)
+            stride = 2 if (b == 0 and st > 0) else 1
+            s[p + "conv1.weight"] = (w * scale, inp, 1, 1)
+            bn(p + "bn1.", w * scale)
+            for i in range(scale):
+                s[p + "convs.%d.weight" % i] = (w, w, 3, 3)
+            for i in range(scale):
+                bn(p + "bns.%d." % i, w)
+            if st >= 2:
+                for j in range(scale - 1):
+                    aff(p + "fuse_models.%d." % j, w)
+            s[p + "conv3.weight"] = (planes * expansion, w * scale, 1, 1)
+            bn(p + "bn3.", planes * expansion)
+            if stride != 1 or inp != planes * expansion:
+                s[p + "shortcut.0.weight"] = (planes * expansion, inp, 1, 1)
+                bn(p + "shortcut.1.", planes * expansion)
+            inp = planes * expansion
+    s["layer3_ds.weight"] = (m * 8 * expansion, m * 4 * expansion, 3, 3)
+    aff("fuse34.", m * 8 * expansion)
+    stats = int(feat_dim / 8) * m * 8
+    s["seg_1.weight"] = (embedding_size, stats * expansion * 2)
+    s["seg_1.bias"] = (embedding_size,)
+    return s
+
+
+def sv_weights(seed: int = 1234, m_channels: int = 64, **spec_args) -> "OrderedDict[str, np.ndarray]":
+    """Seeded tensors for sv_spec: He-scaled convs (std sqrt(2 / fan_in), fan_in = cin * k * k) and plausible eval-mode BN
+    statistics (gamma ~1 +- 0.17, beta / running_mean ~ +-0.17, running_var in 0.5..1.5).  Two damping factors keep the
+    16 residual blocks near unit gain, as a trained network is: the Res2Net 3x3 chain convs at half the He scale and
+    conv3 (the last conv of each residual branch) at 0.25 / sqrt(fan_in).  Activations then stay O(1), the Hardtanh(0, 20)
+    clip is rarely reached (tools/gen_golden_sv.py prints the clipped fraction) and fp32 stays within ~1e-5 of fp64."""
+    out = OrderedDict()
+    for name, shape in sv_spec(m_channels, **spec_args).items():
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        if name.endswith("running_var"):
+            v = _std(name, shape, 0.5 / _SQRT3, seed, mean=1.0)
+        elif name.endswith("running_mean") or (len(shape) == 1 and name.endswith("bias")):
+            v = _std(name, shape, 0.1, seed)
+        elif len(shape) == 1:   # BN gamma
+            v = _std(name, shape, 0.1, seed, mean=1.0)
+        elif name.startswith("seg_1."):
+            v = _std(name, shape, 1.0 / math.sqrt(fan_in), seed)
+        elif name.endswith("conv3.weight"):
+            v = _std(name, shape, 0.25 / math.sqrt(fan_in), seed)
+        elif ".convs." in name:
+            v = _std(name, shape, 0.5 * math.sqrt(2.0 / fan_in), seed)
+        else:
+            v = _std(name, shape, math.sqrt(2.0 / fan_in), seed)
+        out[name] = v
+    return out
+
+
+def write_sv_ckpt(path, seed: int = 1234, m_channels: int = 64, **spec_args):
+    """A torch state-dict file as the reference's pretrained_eres2netv2w24s4ep4.ckpt holds it: sv_weights plus the BN
+    num_batches_tracked counters (int64 scalars)."""
+    import os
+    import torch
+    os.makedirs(os.path.dirname(os.path.abspath(str(path))), exist_ok=True)
+    sd = OrderedDict()
+    for name, a in sv_weights(seed, m_channels, **spec_args).items():
+        sd[name] = torch.from_numpy(a)
+        if name.endswith("running_var"):
+            sd[name[:-len("running_var")] + "num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    torch.save(sd, str(path))
+    return str(path)
+
+
+def sv_feat(i: int, n_frames: int, seed: int = 1234) -> np.ndarray:
+    """fbank-shaped features [n_frames, 80]: log-mel values around -4 with a per-bin tilt and +-2.5 of hashed noise (only
+    IEEE ops of float32, so bit-identical everywhere)."""
+    tilt = np.linspace(1.0, -3.0, 80, dtype=np.float32)[None, :]
+    u = hashed_uniform("svfeat%d" % i, (n_frames, 80), seed)
+    return (np.float32(-4.0) + tilt + np.float32(2.5) * u).astype(np.float32)

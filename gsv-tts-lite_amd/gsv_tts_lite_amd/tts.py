@@ -10,16 +10,18 @@ Drop-in surface kept from the reference:
     load_gpt_model / load_sovits_model / unload_* / get_*_list                 TTS.py:1264-1345
     AudioClip(audio_data, samplerate, audio_len_s, subtitles, orig_text)       Player.py:68-99
 
-CN-HuBERT runs on the device (hubert.py, loaded lazily from models_dir/chinese-hubert-base as TTS.py:111 does).  What
-else sits in front of the hot path in the reference -- G2P text frontends, audio file decoding / resampling, the
-ERes2Net and RoBERTa models -- is OUT OF SCOPE of this build (CPU string processing and
-third-party models whose packages are not installable here).  Their *outputs* enter through the same caches the
-reference keeps:
-    cache_spk_audio(path, ge=...)  or  cache_spk_audio(path, audio=<waveform>, sv_emb=<ERes2Net embedding>)
-                                   (spectrogram + get_ge on the device; the reference: TTS.py:1346, 1576)
-    cache_prompt_audio(path, text, prompt=... | ssl_content=<CN-HuBERT features> | audio=<16 kHz waveform>,
+CN-HuBERT runs on the device (hubert.py, loaded lazily from models_dir/chinese-hubert-base as TTS.py:111 does), and
+so do ERes2NetV2 with its 16 kHz resampling and Kaldi fbank (sv.py, from models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt,
+TTS.py:113).  What else sits in front of the hot path in the reference -- G2P text frontends, audio file decoding, the
+RoBERTa model -- is OUT OF SCOPE of this build (CPU string processing and third-party
+packages not installable here).  Their *outputs* enter through the same caches the reference keeps:
+    cache_spk_audio(path, ge=...)  or  cache_spk_audio(path, audio=<model-rate waveform>[, sv_emb=<ERes2Net embedding>])
+                                   (spectrogram + get_ge on the device, and for v2Pro / v2ProPlus without sv_emb the
+                                   ERes2NetV2 embedding as well; the reference: TTS.py:1346, 1576)
+    cache_prompt_audio(path, text, prompt=... | ssl_content=<CN-HuBERT features> | audio=<waveform>[, sample_rate=16000],
                        phones1=..., bert1=...)
-                                   (CN-HuBERT + extract_latent on the device; TTS.py:1391, 1556)
+                                   (resampling + CN-HuBERT + extract_latent on the device; TTS.py:1391, 1556)
+    verify_speaker(a, b)           cosine similarity of two ERes2NetV2 embeddings (TTS.py:1205-1245)
     set_text_frontend(fn)   fn(text) -> (phones2, word2ph, bert2[P,1024], norm_text)
 With those in place infer()/infer_batched()/infer_stream() behave as in the reference, including
 `return_subtitles=True`: the frame->phoneme alignment runs on the device (subtitles.viterbi_monotonic ->
@@ -159,6 +161,9 @@ class TTS:
         self.cnhubert_path = Path(self.models_dir) / "chinese-hubert-base"
         self.always_load_cnhubert = always_load_cnhubert
         self.cnhubert_model = None
+        self.sv_path = Path(self.models_dir) / "sv" / "pretrained_eres2netv2w24s4ep4.ckpt"
+        self.always_load_sv = always_load_sv
+        self.sv_model = None
         self.gpt_models: dict = {}
         self.sovits_models: dict = {}
         self.spk_audio_cache: dict = {}
@@ -225,34 +230,93 @@ class TTS:
 
     def cache_spk_audio(self, spk_audio_paths, sovits_model=None, ge=None, audio=None, sv_emb=None):
         """TTS.py:1346-1389.  Either the finished embedding `ge` [1, gin, 1], or the reference waveform `audio`
-        (mono fp32 at the model rate, what TTS._load_audio + _resample give) plus, for v2Pro / v2ProPlus, the ERes2Net
-        embedding `sv_emb` [1, 20480]: then the spectrogram (TTS._get_spec) and get_ge run on the device."""
+        (mono fp32 at the model rate, what TTS._load_audio + _resample give): then the spectrogram (TTS._get_spec) and
+        get_ge run on the device.  v2Pro / v2ProPlus add the ERes2Net embedding sv_emb [1, 20480]: the one passed, else the
+        one this path's cache entry holds, else ERes2NetV2 on the device (16 kHz resample + fbank + forward3) from
+        models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, kept loaded only when always_load_sv is set.  Without that
+        checkpoint ge has no sv term (a warning says so).  The entry keeps the sv_emb, so another SoVITS model reuses it."""
         sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
+        entry = self.spk_audio_cache.get(spk_audio_paths)
         if ge is None:
             if audio is None:
-                raise NotImplementedError("decoding / resampling audio files and the ERes2Net model are outside this build's "
-                                          "scope; pass ge=[1, gin, 1], or audio=<waveform> (+ sv_emb=[1, 20480])")
+                raise NotImplementedError("decoding / resampling audio files is outside this build's scope; pass "
+                                          "ge=[1, gin, 1], or audio=<waveform> (+ sv_emb=[1, 20480])")
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
-            vq = self.sovits_models[sovits_model].vq_model
+            sovits = self.sovits_models[sovits_model]
+            vq = sovits.vq_model
             audio = audio.to(self.tts_config.device).float().reshape(1, -1)
             peak = audio.abs().max()
             if peak > 1:                       # TTS.py:1586-1588
                 audio = audio / min(2, float(peak))
+            if sv_emb is None and getattr(vq, "is_v2pro", False):
+                if entry is not None and entry.get("sv_emb") is not None:
+                    sv_emb = entry["sv_emb"]
+                elif os.path.isfile(self.sv_path):
+                    sv_emb = self._sv_embed(audio, self._model_rate(sovits))
+                else:
+                    log.warning("ERes2NetV2 checkpoint %s not found: ge of %s has no speaker-verification term; pass "
+                                "sv_emb=[1, 20480] or install the checkpoint", self.sv_path, spk_audio_paths)
             ge = vq.get_ge(vq.spectrogram(audio), sv_emb)
         entry = self.spk_audio_cache.setdefault(spk_audio_paths, {"ge": {}})
         entry["ge"][sovits_model] = ge.to(self.tts_config.device)
+        if sv_emb is not None:
+            entry["sv_emb"] = torch.as_tensor(sv_emb).to(self.tts_config.device).float().reshape(1, -1)
+
+    @staticmethod
+    def _model_rate(sovits) -> int:
+        try:
+            return int(sovits.hps.data.sampling_rate)
+        except (AttributeError, KeyError, TypeError):
+            return 32000
+
+    def _sv_embed(self, audio, sample_rate):
+        """ERes2Net.compute_embedding3 of a model-rate waveform (TTS._get_spec: resampled to 16 kHz), on the device"""
+        from .sv import load_sv
+        try:
+            if self.sv_model is None:
+                self.sv_model = load_sv(self.sv_path, self.tts_config.device)
+            return self.sv_model.embed(audio, sample_rate)
+        finally:
+            if not self.always_load_sv:
+                self.sv_model = None
+
+    def verify_speaker(self, speaker1_audio, speaker2_audio) -> float:
+        """TTS.py:1205-1245: cosine similarity (eps 1e-6) of two speakers' ERes2NetV2 embeddings.  Each argument is a
+        cache_spk_audio key whose entry holds an sv_emb, or a mono fp32 waveform at the model rate (that of the first
+        loaded SoVITS model, 32 kHz when none is loaded), peak-normalised here as TTS._get_spec does."""
+        def emb(a):
+            if isinstance(a, (str, Path)):
+                e = self.spk_audio_cache.get(a, {}).get("sv_emb")
+                if e is None:
+                    raise NotImplementedError("decoding / resampling audio files is outside this build's scope; cache %r "
+                                              "with cache_spk_audio(audio=...) first, or pass its waveform" % (a,))
+                return e.to(self.tts_config.device).float().reshape(1, -1)
+            w = torch.as_tensor(a).to(self.tts_config.device).float().reshape(1, -1)
+            peak = w.abs().max()
+            if peak > 1:
+                w = w / min(2, float(peak))
+            rate = self._model_rate(next(iter(self.sovits_models.values()))) if self.sovits_models else 32000
+            return self._sv_embed(w, rate)
+        try:
+            e1, e2 = emb(speaker1_audio), emb(speaker2_audio)
+            return float(torch.cosine_similarity(e1, e2, dim=-1, eps=1e-6).item())
+        finally:
+            self._empty_cache()
 
     def cache_prompt_audio(self, prompt_audio_paths, prompt_audio_texts, prompt=None, phones1=None, bert1=None,
-                           ssl_content=None, sovits_model=None, audio=None):
+                           ssl_content=None, sovits_model=None, audio=None, sample_rate=16000):
         """TTS.py:1391-1440.  `prompt` int64 [1, Ly], or `ssl_content` [1, 768, Th] (CN-HuBERT last_hidden_state,
         transposed as in TTS._get_prompt), or `audio`, the prompt waveform as mono fp32 at 16 kHz ([n] or [1, n]): then
         CN-HuBERT (TTS._get_prompt: + 0.3 s of zeros) and extract_latent run on the device.  CN-HuBERT is loaded from
-        models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Resampling from
-        other rates is not part of this build: the caller brings 16 kHz audio."""
+        models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Audio at another
+        `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample)."""
         if not prompt_audio_texts:
             raise ValueError("prompt_audio_text must not be empty")
         if prompt is None and ssl_content is None and audio is not None:
+            if int(sample_rate) != 16000:
+                from .sv import resample
+                audio = resample(audio, int(sample_rate), 16000, self.tts_config.device)
             ssl_content = self._cnhubert_ssl(audio)
         if prompt is None and ssl_content is not None:
             sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)

@@ -335,8 +335,8 @@ int gsv_sola(const float* prev_tail, const float* chunk, int n, int overlap, int
  *   gsv_ref_extract_latent  SynthesizerTrn.extract_latent (models.py:431-434): ssl_proj (k 2, stride 2) and the
  *                           nearest-codebook search of EuclideanCodebook.quantize (module/core_vq.py:124-128)
  * Tensors ("ref_enc.*", "sv_emb.*", "prelu.weight", "ssl_proj.*", "quantizer.vq.layers.0._codebook.embed") are
- * given under their checkpoint names, device fp32, before finalize.  `ssl` comes from CN-HuBERT (gsv_hubert_* below);
- * audio decoding / resampling and the ERes2Net model that produces `sv_emb` are outside this library. */
+ * given under their checkpoint names, device fp32, before finalize.  `ssl` comes from CN-HuBERT (gsv_hubert_* below),
+ * `sv_emb` from ERes2NetV2 (gsv_sv_* below); audio decoding is outside this library. */
 typedef struct gsv_ref gsv_ref;
 typedef struct gsv_ref_config {
     int n_fft;      /* hps.data.filter_length == win_length (2048) */
@@ -404,6 +404,50 @@ size_t gsv_hubert_workspace(gsv_hubert* h, int n_samples);
  * (last_hidden_state transposed, what gsv_ref_extract_latent takes).  Nothing is allocated. */
 int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* ssl, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* ERes2NetV2, once per new speaker: the speaker-verification embedding sv_emb that get_ge adds for v2Pro / v2ProPlus, as
+ * TTS.cache_spk_audio computes it (gsv_tts/TTS.py:1346-1389, 1591-1610; GPT_SoVITS/SV/sv.py): the model-rate waveform
+ * resampled to 16 kHz (torchaudio Resample defaults), an 80-bin Kaldi fbank (dither 0), then
+ * ERes2NetV2(baseWidth=24, scale=4, expansion=4).forward3, fp32 in every mode.  Tensors under the checkpoint's
+ * state-dict names ("conv1.*", "bn1.*", "layer1..4.*", "layer3_ds.*", "fuse34.*"), device fp32, before finalize; BN
+ * (eval, eps 1e-5) is folded at finalize.  seg_1.*, pool.* and num_batches_tracked are not read by forward3: leave them
+ * out.  Bit-reproducible (no atomics). */
+typedef struct gsv_sv gsv_sv;
+typedef struct gsv_sv_config {
+    int m_channels;   /* stem channels (64); stage s has planes m_channels << s and 4 * planes output channels */
+    int blocks[4];    /* blocks per stage ([3, 4, 6, 3]) */
+    int width[4];     /* Res2Net split width per stage, floor(planes * baseWidth / 64) (24, 48, 96, 192); >= 4 */
+    int scale;        /* splits per block: 4 only */
+    int expansion;    /* 4 only */
+    int feat_dim;     /* fbank bins: 80 only */
+} gsv_sv_config;
+/* refuses (GSV_ERR_ARG) any other scale, expansion or feat_dim */
+int gsv_sv_create(const gsv_sv_config* cfg, gsv_sv** out);
+int gsv_sv_destroy(gsv_sv* h);
+int gsv_sv_load_tensor(gsv_sv* h, const char* name, const float* data, int64_t numel, void* stream);
+int gsv_sv_finalize(gsv_sv* h, void* stream);
+/* ceil(new * n / orig) with the rates reduced by their gcd (n when the rates are equal); 0 on bad arguments */
+int gsv_sv_resample_length(int n_samples, int orig_sr, int new_sr);
+/* device bytes gsv_sv_resample needs for this rate pair (its fp32 kernel table) */
+size_t gsv_sv_resample_workspace(int orig_sr, int new_sr);
+/* torchaudio.transforms.Resample(orig_sr, new_sr) with default arguments: x fp32 [n] -> y fp32
+ * [gsv_sv_resample_length(n, orig_sr, new_sr)].  Needs no model handle. */
+int gsv_sv_resample(const float* x, int n_samples, int orig_sr, int new_sr, float* y, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* fbank frames of a waveform of n_samples at sample_rate once it is at 16 kHz: 1 + (n16 - 400) / 160, 0 if n16 < 400 */
+int gsv_sv_frames(gsv_sv* h, int n_samples, int sample_rate);
+/* device bytes of the caller-owned workspace of gsv_sv_embed over n_samples at sample_rate; it also covers
+ * gsv_sv_resample of that input, and gsv_sv_fbank / gsv_sv_forward of what it resamples to.  0 when too short. */
+size_t gsv_sv_workspace(gsv_sv* h, int n_samples, int sample_rate);
+/* wav fp32 [n_samples] at 16 kHz -> feat fp32 [frames][80], Kaldi.fbank(num_mel_bins=80, sample_frequency=16000, dither=0) */
+int gsv_sv_fbank(gsv_sv* h, const float* wav16k, int n_samples, float* feat, void* workspace, size_t workspace_bytes,
+                 void* stream);
+/* feat fp32 [n_frames][80] -> sv_emb fp32 [4 * 8 * m_channels * 10] = forward3(feat[None]), index c * 10 + f */
+int gsv_sv_forward(gsv_sv* h, const float* feat, int n_frames, float* sv_emb, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* wav fp32 [n_samples] at sample_rate (mono, peak-normalised by the caller) -> resample to 16 kHz -> fbank -> sv_emb */
+int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, float* sv_emb, void* workspace,
+                 size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
