@@ -1,6 +1,7 @@
 // C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section; kernels in refaudio.h), of
 // CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm) and of ERes2NetV2 with its resampler and
-// fbank (gsv_sv_*; kernels in sv.h, which uses the same fgemm for the DFT and the mel filter bank).
+// fbank (gsv_sv_*; kernels in sv.h, which uses the same fgemm for the DFT and the mel filter bank) and of Chinese RoBERTa
+// (gsv_roberta_*; kernels in roberta.h, which reuses hubert.h's LayerNorm and fgemm's tile body).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include "gsv_error.h"
 #include "hubert.h"
 #include "refaudio.h"
+#include "roberta.h"
 #include "sv.h"
 
 using namespace gsv;
@@ -997,6 +999,247 @@ int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, fl
     }
     if ((rc = sv_fbank_run(h, st, x16, T, w.feat, w))) return rc;
     return sv_forward_run(h, st, w.feat, T, sv_emb, w);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// Chinese RoBERTa (BertForMaskedLM hidden_states[-3]): packed texts -> hidden rows -> phone features
+// ------------------------------------------------------------------------------------------------------------------
+struct gsv_roberta {
+    gsv_roberta_config cfg;
+    std::map<std::string, std::pair<float*, int64_t>> t;   // loaded tensors (device, fp32)
+    bool finalized = false;
+    // derived at finalize
+    std::vector<float*> w_qkv, b_qkv;                       // per run layer [3H][H], [3H] (query, key, value)
+    std::vector<void*> owned;
+};
+
+namespace {
+
+const float* RT(gsv_roberta* h, const std::string& name) { return h->t.at(name).first; }
+
+std::string rb_layer(int l, const char* rest) { return "encoder.layer." + std::to_string(l) + "." + rest; }
+
+// layers that feed hidden_states[-3]: 0 .. n_layer - 3
+int rb_run_layers(const gsv_roberta_config& c) { return c.n_layer - 2; }
+
+// floats of the split-K partial buffer of one M-row GEMM with N outputs over K
+size_t rb_part(int M, int N, int K) { return (size_t)rb_splits(N, K) * M * N; }
+
+struct RbWs {
+    float *x, *tmp, *qkv, *att, *ffn, *part, *hid;
+    size_t total;
+};
+RbWs rb_carve(const gsv_roberta_config& c, int rows, float* base) {
+    RbWs w;
+    size_t off = 0;
+    auto take = [&](size_t n) { float* r = base ? base + off : nullptr; off += up(n); return r; };
+    const size_t M = rows, H = c.hidden, F = c.ffn;
+    const size_t part = std::max({rb_part(rows, 3 * c.hidden, c.hidden), rb_part(rows, c.hidden, c.hidden),
+                                  rb_part(rows, c.ffn, c.hidden), rb_part(rows, c.hidden, c.ffn)});
+    w.x = take(M * H);
+    w.tmp = take(M * H);
+    w.qkv = take(M * 3 * H);
+    w.att = take(M * H);
+    w.ffn = take(M * F);
+    w.part = take(part);
+    w.hid = take(M * H);
+    w.total = off;
+    return w;
+}
+
+// Y[M][N] = act(X . W^T + bias) (+ R): roberta.h's split-K GEMM (summation order fixed by N and K)
+int rb_gemm(hipStream_t st, const float* X, const float* W, float* Y, int M, int N, int K, const float* bias, int act,
+            const float* R, float* part) {
+    const int S = rb_splits(N, K);
+    rb_splitk_kernel<<<dim3((N + 63) / 64, (M + 63) / 64, S), 256, 0, st>>>(X, W, part, M, N, K, S);
+    const long long n4 = (long long)M * N / 4;
+    rb_splitk_reduce_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(part, S, n4, N, bias, act, R, Y);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int rb_check_call(gsv_roberta* h, const int* ids, const int* starts, int n_seq, int rows, int max_len, void* workspace,
+                  size_t workspace_bytes) {
+    if (!h || !ids || !starts || !workspace) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (!h->finalized) return abi_fail(GSV_ERR_STATE, "roberta: not finalized");
+    if (n_seq < 1 || rows < n_seq * 2 || max_len < 2 || max_len > h->cfg.max_pos || max_len > rows ||
+        (long long)max_len * n_seq < rows)
+        return abi_fail(GSV_ERR_ARG, "roberta: %d texts over %d rows with max_len %d unsupported (2 <= len <= max_len <= %d)",
+                        n_seq, rows, max_len, h->cfg.max_pos);
+    if (workspace_bytes < gsv_roberta_workspace(h, rows, n_seq, max_len)) return abi_fail(GSV_ERR_ARG, "roberta: workspace too small");
+    if ((reinterpret_cast<size_t>(workspace) & 15) != 0) return abi_fail(GSV_ERR_ARG, "roberta: workspace must be 16-byte aligned");
+    return GSV_OK;
+}
+
+// hidden_states[-3] of the packed texts into out [rows][H]
+int rb_run(gsv_roberta* h, hipStream_t st, const int* ids, const int* starts, int n_seq, int rows, int max_len, float* out,
+           const RbWs& w) {
+    const gsv_roberta_config& c = h->cfg;
+    const int H = c.hidden, F = c.ffn, L = rb_run_layers(c);
+    int bad = 0;
+    rb_embed_ln_kernel<<<(rows + 3) / 4, 256, 0, st>>>(ids, starts, n_seq, rows, RT(h, "embeddings.word_embeddings.weight"), c.vocab,
+                                                       RT(h, "embeddings.position_embeddings.weight"), c.max_pos,
+                                                       RT(h, "embeddings.token_type_embeddings.weight"), H,
+                                                       RT(h, "embeddings.LayerNorm.weight"), RT(h, "embeddings.LayerNorm.bias"), c.eps,
+                                                       L > 0 ? w.x : out);
+    const float scale = 1.f / sqrtf(64.f);
+    for (int l = 0; l < L; ++l) {
+        bad |= rb_gemm(st, w.x, h->w_qkv[l], w.qkv, rows, 3 * H, H, h->b_qkv[l], 0, nullptr, w.part);
+        rb_attn_kernel<<<dim3((max_len + ATT_QB - 1) / ATT_QB, c.n_head, n_seq), 128, 0, st>>>(w.qkv, starts, rows, H, scale, w.att);
+        bad |= rb_gemm(st, w.att, RT(h, rb_layer(l, "attention.output.dense.weight")), w.tmp, rows, H, H,
+                       RT(h, rb_layer(l, "attention.output.dense.bias")), 0, w.x, w.part);
+        bad |= ln(st, w.tmp, w.x, rows, H, RT(h, rb_layer(l, "attention.output.LayerNorm.weight")),
+                  RT(h, rb_layer(l, "attention.output.LayerNorm.bias")), c.eps);
+        bad |= rb_gemm(st, w.x, RT(h, rb_layer(l, "intermediate.dense.weight")), w.ffn, rows, F, H,
+                       RT(h, rb_layer(l, "intermediate.dense.bias")), 2, nullptr, w.part);
+        bad |= rb_gemm(st, w.ffn, RT(h, rb_layer(l, "output.dense.weight")), w.tmp, rows, H, F,
+                       RT(h, rb_layer(l, "output.dense.bias")), 0, w.x, w.part);
+        bad |= ln(st, w.tmp, l == L - 1 ? out : w.x, rows, H, RT(h, rb_layer(l, "output.LayerNorm.weight")),
+                  RT(h, rb_layer(l, "output.LayerNorm.bias")), c.eps);
+    }
+    if (bad) return abi_fail(GSV_ERR_HIP, "roberta: a forward launch failed");
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsv_roberta_create(const gsv_roberta_config* cfg, gsv_roberta** out) {
+    if (!cfg || !out) return abi_fail(GSV_ERR_ARG, "null argument");
+    const gsv_roberta_config& c = *cfg;
+    if (c.hidden < 64 || c.hidden % 64 || c.hidden > 64 * LN_MAX_NPL)
+        return abi_fail(GSV_ERR_ARG, "roberta: hidden %d unsupported (a multiple of 64 up to %d)", c.hidden, 64 * LN_MAX_NPL);
+    if (c.n_head < 1 || c.hidden != 64 * c.n_head)
+        return abi_fail(GSV_ERR_ARG, "roberta: %d heads over hidden %d unsupported (the attention kernel needs head dim 64)", c.n_head, c.hidden);
+    if (c.n_layer < 2) return abi_fail(GSV_ERR_ARG, "roberta: n_layer %d unsupported (hidden_states[-3] needs at least 2)", c.n_layer);
+    if (c.ffn < 64 || c.ffn % 64) return abi_fail(GSV_ERR_ARG, "roberta: intermediate size %d unsupported (a multiple of 64)", c.ffn);
+    if (c.vocab < 1 || c.type_vocab < 1 || c.max_pos < 2)
+        return abi_fail(GSV_ERR_ARG, "roberta: vocab %d / type_vocab %d / max_pos %d unsupported", c.vocab, c.type_vocab, c.max_pos);
+    if (!(c.eps > 0.f)) return abi_fail(GSV_ERR_ARG, "roberta: layer_norm_eps must be > 0");
+    gsv_roberta* h = new gsv_roberta();
+    h->cfg = c;
+    *out = h;
+    return GSV_OK;
+}
+
+int gsv_roberta_destroy(gsv_roberta* h) {
+    if (!h) return GSV_OK;
+    for (auto& kv : h->t) (void)hipFree(kv.second.first);
+    for (void* p : h->owned) (void)hipFree(p);
+    delete h;
+    return GSV_OK;
+}
+
+int gsv_roberta_load_tensor(gsv_roberta* h, const char* name, const float* data, int64_t numel, void* stream) {
+    if (!h || !name || !data || numel < 1) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return abi_fail(GSV_ERR_STATE, "roberta: load after finalize");
+    const std::string n(name);
+    if (n.rfind("embeddings.", 0) == 0) {
+        // every embeddings.* tensor is read
+    } else if (n.rfind("encoder.layer.", 0) == 0) {
+        const int l = std::atoi(n.c_str() + std::strlen("encoder.layer."));
+        if (l >= rb_run_layers(h->cfg))
+            return abi_fail(GSV_ERR_ARG, "roberta: %s is past hidden_states[-3] (only encoder.layer.0 .. %d run)", name,
+                            rb_run_layers(h->cfg) - 1);
+    } else {
+        return abi_fail(GSV_ERR_ARG, "roberta: unknown tensor %s (pooler / cls.* are not read)", name);
+    }
+    float* d = nullptr;
+    RCHK(hipMalloc(reinterpret_cast<void**>(&d), numel * sizeof(float)));
+    RCHK(hipMemcpyAsync(d, data, numel * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+    auto it = h->t.find(n);
+    if (it != h->t.end()) (void)hipFree(it->second.first);
+    h->t[n] = {d, numel};
+    return GSV_OK;
+}
+
+int gsv_roberta_finalize(gsv_roberta* h, void* stream) {
+    if (!h) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (h->finalized) return GSV_OK;
+    const gsv_roberta_config& c = h->cfg;
+    const int64_t H = c.hidden, F = c.ffn;
+    const int L = rb_run_layers(c);
+    std::vector<std::pair<std::string, int64_t>> need = {
+        {"embeddings.word_embeddings.weight", (int64_t)c.vocab * H},
+        {"embeddings.position_embeddings.weight", (int64_t)c.max_pos * H},
+        {"embeddings.token_type_embeddings.weight", (int64_t)c.type_vocab * H},
+        {"embeddings.LayerNorm.weight", H}, {"embeddings.LayerNorm.bias", H},
+    };
+    for (int l = 0; l < L; ++l) {
+        for (const char* p : {"attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"}) {
+            need.push_back({rb_layer(l, p) + ".weight", H * H});
+            need.push_back({rb_layer(l, p) + ".bias", H});
+        }
+        need.push_back({rb_layer(l, "intermediate.dense.weight"), F * H});
+        need.push_back({rb_layer(l, "intermediate.dense.bias"), F});
+        need.push_back({rb_layer(l, "output.dense.weight"), H * F});
+        need.push_back({rb_layer(l, "output.dense.bias"), H});
+        for (const char* p : {"attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias", "output.LayerNorm.weight",
+                              "output.LayerNorm.bias"})
+            need.push_back({rb_layer(l, p), H});
+    }
+    for (const auto& n : need) {
+        auto it = h->t.find(n.first);
+        if (it == h->t.end()) return abi_fail(GSV_ERR_STATE, "roberta: tensor %s was not loaded", n.first.c_str());
+        if (it->second.second != n.second)
+            return abi_fail(GSV_ERR_ARG, "roberta: tensor %s has %lld elements, expected %lld", n.first.c_str(),
+                            (long long)it->second.second, (long long)n.second);
+    }
+    hipStream_t st = S(stream);
+    h->w_qkv.assign(L, nullptr);
+    h->b_qkv.assign(L, nullptr);
+    const char* p[3] = {"attention.self.query", "attention.self.key", "attention.self.value"};
+    for (int l = 0; l < L; ++l) {
+        for (float** q : {&h->w_qkv[l], &h->b_qkv[l]}) {
+            RCHK(hipMalloc(reinterpret_cast<void**>(q), (q == &h->w_qkv[l] ? 3 * H * H : 3 * H) * sizeof(float)));
+            h->owned.push_back(*q);
+        }
+        for (int j = 0; j < 3; ++j) {
+            RCHK(hipMemcpyAsync(h->w_qkv[l] + j * H * H, RT(h, rb_layer(l, p[j]) + ".weight"), H * H * 4, hipMemcpyDeviceToDevice, st));
+            RCHK(hipMemcpyAsync(h->b_qkv[l] + j * H, RT(h, rb_layer(l, p[j]) + ".bias"), H * 4, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    // the separate q / k / v copies are not read again: free them once the fused copies are made
+    RCHK(hipStreamSynchronize(st));
+    for (int l = 0; l < L; ++l)
+        for (int j = 0; j < 3; ++j)
+            for (const char* suf : {".weight", ".bias"}) {
+                auto it = h->t.find(rb_layer(l, p[j]) + suf);
+                RCHK(hipFree(it->second.first));
+                h->t.erase(it);
+            }
+    h->finalized = true;
+    return GSV_OK;
+}
+
+size_t gsv_roberta_workspace(gsv_roberta* h, int total_rows, int n_seq, int max_len) {
+    if (!h || total_rows < 1 || n_seq < 1 || max_len < 1) return 0;
+    return sizeof(float) * rb_carve(h->cfg, total_rows, nullptr).total;
+}
+
+int gsv_roberta_forward(gsv_roberta* h, const int* ids, const int* seq_starts, int n_seq, int total_rows, int max_len,
+                        float* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc;
+    if ((rc = rb_check_call(h, ids, seq_starts, n_seq, total_rows, max_len, workspace, workspace_bytes))) return rc;
+    if (!hidden_out) return abi_fail(GSV_ERR_ARG, "null argument");
+    const RbWs w = rb_carve(h->cfg, total_rows, static_cast<float*>(workspace));
+    return rb_run(h, S(stream), ids, seq_starts, n_seq, total_rows, max_len, hidden_out, w);
+}
+
+int gsv_roberta_features(gsv_roberta* h, const int* ids, const int* seq_starts, int n_seq, int total_rows, int max_len,
+                         const int* phone_index, int n_phones, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc;
+    if ((rc = rb_check_call(h, ids, seq_starts, n_seq, total_rows, max_len, workspace, workspace_bytes))) return rc;
+    if (n_phones < 0 || (n_phones > 0 && (!phone_index || !out))) return abi_fail(GSV_ERR_ARG, "roberta: %d phones", n_phones);
+    hipStream_t st = S(stream);
+    const RbWs w = rb_carve(h->cfg, total_rows, static_cast<float*>(workspace));
+    if ((rc = rb_run(h, st, ids, seq_starts, n_seq, total_rows, max_len, w.hid, w))) return rc;
+    if (n_phones > 0) rb_phone_gather_kernel<<<n_phones, 256, 0, st>>>(w.hid, total_rows, h->cfg.hidden, phone_index, out);
+    RCHK(hipGetLastError());
+    return GSV_OK;
 }
 
 }  // extern "C"

@@ -30,6 +30,8 @@ EXPORTS = [
     "gsv_sv_create", "gsv_sv_destroy", "gsv_sv_load_tensor", "gsv_sv_finalize", "gsv_sv_resample_length",
     "gsv_sv_resample_workspace", "gsv_sv_resample", "gsv_sv_frames", "gsv_sv_workspace", "gsv_sv_fbank", "gsv_sv_forward",
     "gsv_sv_embed",
+    "gsv_roberta_create", "gsv_roberta_destroy", "gsv_roberta_load_tensor", "gsv_roberta_finalize", "gsv_roberta_workspace",
+    "gsv_roberta_forward", "gsv_roberta_features",
 ]
 
 
@@ -69,6 +71,11 @@ class HubertConfig(ctypes.Structure):
 class SvConfig(ctypes.Structure):
     _fields_ = [("m_channels", ctypes.c_int), ("blocks", ctypes.c_int * 4), ("width", ctypes.c_int * 4),
                 ("scale", ctypes.c_int), ("expansion", ctypes.c_int), ("feat_dim", ctypes.c_int)]
+
+
+class RobertaConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "n_layer", "n_head", "ffn", "vocab", "max_pos", "type_vocab")] + [
+        ("eps", ctypes.c_float)]
 
 
 _LIB = None
@@ -145,6 +152,12 @@ def lib():
         "gsv_sv_fbank": [vp, vp, i, vp, vp, sz, vp],
         "gsv_sv_forward": [vp, vp, i, vp, vp, sz, vp],
         "gsv_sv_embed": [vp, vp, i, i, vp, vp, sz, vp],
+        "gsv_roberta_create": [ctypes.POINTER(RobertaConfig), ctypes.POINTER(vp)],
+        "gsv_roberta_destroy": [vp],
+        "gsv_roberta_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
+        "gsv_roberta_finalize": [vp, vp],
+        "gsv_roberta_forward": [vp, vp, vp, i, i, i, vp, vp, sz, vp],
+        "gsv_roberta_features": [vp, vp, vp, i, i, i, vp, i, vp, vp, sz, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -168,6 +181,8 @@ def lib():
     L.gsv_sv_resample_workspace.restype = sz
     L.gsv_sv_workspace.argtypes = [vp, i, i]
     L.gsv_sv_workspace.restype = sz
+    L.gsv_roberta_workspace.argtypes = [vp, i, i, i]
+    L.gsv_roberta_workspace.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

@@ -231,6 +231,46 @@ def read_cnhubert(path):
     return config, weights
 
 
+def read_roberta(path):
+    """(config dict, state dict) of a Hugging Face chinese-roberta-wwm-ext-large directory (TTS.cnroberta_path =
+    models_dir/chinese-roberta-wwm-ext-large, gsv_tts/TTS.py:112): config.json plus model.safetensors or pytorch_model.bin
+    (weights_only), keys with or without the "bert." prefix (old LayerNorm gamma / beta names become weight / bias).  Only
+    what hidden_states[-3] reads is kept: cls.*, the pooler and the last two encoder layers are dropped.  Configurations
+    this build does not run are refused here (roberta.check_config).  Device-free; the tokenizer is read separately
+    (roberta.WordPieceTokenizer.from_dir)."""
+    from .roberta import check_config, used_tensor
+    path = str(path)
+    cfg_path = os.path.join(path, "config.json")
+    if not os.path.isfile(cfg_path):
+        raise FileNotFoundError("RoBERTa: %s has no config.json (a Hugging Face chinese-roberta-wwm-ext-large directory is "
+                                "expected)" % path)
+    with open(cfg_path) as f:
+        config = json.load(f)
+    config = dict(config, **check_config(config))
+    st = os.path.join(path, "model.safetensors")
+    pt = os.path.join(path, "pytorch_model.bin")
+    if os.path.isfile(st):
+        from safetensors.torch import load_file
+        raw = load_file(st)
+    elif os.path.isfile(pt):
+        raw = torch.load(pt, map_location="cpu", weights_only=True)
+    else:
+        raise FileNotFoundError("RoBERTa: %s holds neither model.safetensors nor pytorch_model.bin" % path)
+    weights = {}
+    for k, v in raw.items():
+        if k.startswith("bert."):
+            k = k[len("bert."):]
+        if k.endswith("LayerNorm.gamma"):
+            k = k[:-len("gamma")] + "weight"
+        elif k.endswith("LayerNorm.beta"):
+            k = k[:-len("beta")] + "bias"
+        if used_tensor(k, config["num_hidden_layers"]):
+            weights[k] = v.float()
+    if "embeddings.word_embeddings.weight" not in weights:
+        raise ValueError("RoBERTa: %s has no embeddings.word_embeddings.weight (a BERT state dict is expected)" % path)
+    return config, weights
+
+
 def read_sv(path):
     """The ERes2NetV2 state dict of a speaker-verification checkpoint (TTS.sv_path =
     models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, gsv_tts/TTS.py:113; SV/sv.py loads it with torch.load): a torch file

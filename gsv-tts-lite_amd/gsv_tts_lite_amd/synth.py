@@ -655,3 +655,141 @@ def sv_feat(i: int, n_frames: int, seed: int = 1234) -> np.ndarray:
     tilt = np.linspace(1.0, -3.0, 80, dtype=np.float32)[None, :]
     u = hashed_uniform("svfeat%d" % i, (n_frames, 80), seed)
     return (np.float32(-4.0) + tilt + np.float32(2.5) * u).astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------
+# Chinese RoBERTa (transformers BertForMaskedLM, chinese-roberta-wwm-ext-large shapes) -- tts_config.cnroberta
+# --------------------------------------------------------------------------------------
+def roberta_config(**overrides) -> dict:
+    """config.json fields of chinese-roberta-wwm-ext-large, with overrides."""
+    cfg = dict(model_type="bert", hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096,
+               vocab_size=21128, max_position_embeddings=512, type_vocab_size=2, layer_norm_eps=1e-12, hidden_act="gelu",
+               position_embedding_type="absolute", hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1,
+               initializer_range=0.02, pad_token_id=0)
+    cfg.update(overrides)
+    return cfg
+
+
+def roberta_spec(cfg: dict, run_only: bool = False) -> "OrderedDict[str, tuple]":
+    """BertModel state-dict names (no "bert." prefix) and shapes; run_only: only what hidden_states[-3] reads (the last two
+    layers left out)"""
+    H, F, L = cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"]
+    s = OrderedDict()
+    s["embeddings.word_embeddings.weight"] = (cfg["vocab_size"], H)
+    s["embeddings.position_embeddings.weight"] = (cfg["max_position_embeddings"], H)
+    s["embeddings.token_type_embeddings.weight"] = (cfg["type_vocab_size"], H)
+    s["embeddings.LayerNorm.weight"] = (H,)
+    s["embeddings.LayerNorm.bias"] = (H,)
+    for l in range(L - 2 if run_only else L):
+        p = "encoder.layer.%d." % l
+        for n in ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"):
+            s[p + n + ".weight"] = (H, H)
+            s[p + n + ".bias"] = (H,)
+        s[p + "attention.output.LayerNorm.weight"] = (H,)
+        s[p + "attention.output.LayerNorm.bias"] = (H,)
+        s[p + "intermediate.dense.weight"] = (F, H)
+        s[p + "intermediate.dense.bias"] = (F,)
+        s[p + "output.dense.weight"] = (H, F)
+        s[p + "output.dense.bias"] = (H,)
+        s[p + "output.LayerNorm.weight"] = (H,)
+        s[p + "output.LayerNorm.bias"] = (H,)
+    return s
+
+
+def roberta_weights(cfg: dict = None, seed: int = 1234, run_only: bool = False) -> "OrderedDict[str, np.ndarray]":
+    """Seeded tensors for roberta_spec.  Every sublayer ends in a LayerNorm, so activations stay O(1) through all layers:
+    1/sqrt(fan_in) linears, query / key at 1.5x for attention logits with a spread of a few units, unit embeddings, LN
+    gains 1 +- 0.1."""
+    cfg = cfg or roberta_config()
+    out = OrderedDict()
+    for name, shape in roberta_spec(cfg, run_only).items():
+        fan_in = shape[1] if len(shape) > 1 else 1
+        if "LayerNorm" in name:
+            v = _std(name, shape, 0.1, seed, mean=1.0 if name.endswith("weight") else 0.0)
+        elif name.startswith("embeddings."):
+            v = _std(name, shape, 1.0, seed)
+        elif name.endswith(("query.weight", "key.weight")):
+            v = _std(name, shape, 1.5 / math.sqrt(fan_in), seed)
+        elif name.endswith("weight"):
+            v = _std(name, shape, 1.0 / math.sqrt(fan_in), seed)
+        else:
+            v = _std(name, shape, 0.05, seed)
+        out[name] = v
+    return out
+
+
+_ROBERTA_CJK = ("的一是不了人我在有他这中大来上国个到说们为子和你地出道也时年得就那要下以生会自着去之过家学对可她里后小么心多天而"
+                "能好都然没日于起还发成事只作当想看文无开手十用主行方又如前所本见经头面公同三已老从动两长知民样现分将外但身些与高"
+                "意进把法此实回二理美点月明其种声全工己话儿者向情部正名定女问力机给等几很业最间新什打便位因重被走电四第门相次东政"
+                "海口使教西再平真听世气信北少关并内加化由却代军产入先山五太水万市眼体别处总才场师书比住员九笑性通目华报立马命张活"
+                "难神数件安表原车白应路期叫死常提感金何更反合放做系计或司利受光王果亲界及今京务制解各任至清物台象记边共风战干接它"
+                "许八特觉望直服毛林题建南度色字请交爱让认算论百吃义科怎元社术结六功指思非流每青管夫连远资队跟带花快条院变联言权往"
+                "展该领传近留红治决周保达办运武半候七必城父强步完革深区即求品士转量空甚众技轻程告江语英基派满式李息写呢识极令黄德"
+                "收脸钱党倒未持取设始版双历越史商千片容研像找友孩站广改议形委早房音火际则首单据导影失拿网香似斯专石若兵弟谁校读志"
+                "飞观争究包组造落视济喜离虽坏兴切")
+
+
+def roberta_vocab() -> list:
+    """A small BERT-Chinese-style vocabulary (tokens in id order): the five specials, digits, Latin letters and a few
+    words with ## pieces, ASCII and full-width punctuation, a few hundred common CJK characters."""
+    toks = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"]
+    toks += list("0123456789") + ["10", "2024", "##0", "##5"]
+    toks += [chr(c) for c in range(ord("a"), ord("z") + 1)] + ["##" + chr(c) for c in range(ord("a"), ord("z") + 1)]
+    toks += ["hello", "world", "the", "un", "##able", "##ing", "##s", "##ed", "ai", "gpu", "cafe", "naive"]
+    toks += list("!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~") + list("，。！？、：；（）《》“”‘’…—·")
+    toks += list(_ROBERTA_CJK)
+    return list(dict.fromkeys(toks))
+
+
+def roberta_tokenizer_json(vocab: list = None) -> dict:
+    """tokenizer.json (the tokenizers library's BertNormalizer + BertPreTokenizer + WordPiece layout) over `vocab`"""
+    vocab = vocab or roberta_vocab()
+    ids = {t: i for i, t in enumerate(vocab)}
+    specials = [t for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]") if t in ids]
+    return {
+        "version": "1.0", "truncation": None, "padding": None,
+        "added_tokens": [{"id": ids[t], "content": t, "single_word": False, "lstrip": False, "rstrip": False,
+                          "normalized": False, "special": True} for t in specials],
+        "normalizer": {"type": "BertNormalizer", "clean_text": True, "handle_chinese_chars": True, "strip_accents": None,
+                       "lowercase": True},
+        "pre_tokenizer": {"type": "BertPreTokenizer"},
+        "post_processor": {"type": "TemplateProcessing",
+                           "single": [{"SpecialToken": {"id": "[CLS]", "type_id": 0}}, {"Sequence": {"id": "A", "type_id": 0}},
+                                      {"SpecialToken": {"id": "[SEP]", "type_id": 0}}],
+                           "special_tokens": {t: {"id": t, "ids": [ids[t]], "tokens": [t]} for t in ("[CLS]", "[SEP]")}},
+        "decoder": {"type": "WordPiece", "prefix": "##", "cleanup": True},
+        "model": {"type": "WordPiece", "unk_token": "[UNK]", "continuing_subword_prefix": "##",
+                  "max_input_chars_per_word": 100, "vocab": ids},
+    }
+
+
+def write_roberta_dir(path, cfg: dict = None, seed: int = 1234, fmt: str = "safetensors", prefix: bool = True,
+                      with_head: bool = True):
+    """A Hugging Face directory (config.json, model.safetensors or pytorch_model.bin, tokenizer.json) holding
+    roberta_weights(cfg, seed) under "bert.*" (prefix) or bare names, plus a cls.* MLM head (with_head) the runtime must
+    ignore.  Keep num_hidden_layers small: the full model is 1.3 GB of fp32."""
+    import json
+    import os
+    import torch
+    cfg = cfg or roberta_config()
+    os.makedirs(path, exist_ok=True)
+    pre = "bert." if prefix else ""
+    sd = OrderedDict((pre + k, torch.from_numpy(a)) for k, a in roberta_weights(cfg, seed).items())
+    if with_head:
+        H = cfg["hidden_size"]
+        for k, shape in (("cls.predictions.bias", (cfg["vocab_size"],)), ("cls.predictions.transform.dense.weight", (H, H)),
+                         ("cls.predictions.transform.dense.bias", (H,)), ("cls.predictions.transform.LayerNorm.weight", (H,)),
+                         ("cls.predictions.transform.LayerNorm.bias", (H,))):
+            sd[k] = torch.from_numpy(_std(k, shape, 0.02, seed))
+    with open(os.path.join(path, "config.json"), "w") as f:
+        json.dump(dict(cfg, architectures=["BertForMaskedLM"]), f, indent=1)
+    with open(os.path.join(path, "tokenizer.json"), "w", encoding="utf-8") as f:
+        json.dump(roberta_tokenizer_json(), f, ensure_ascii=False)
+    if fmt == "safetensors":
+        from safetensors.torch import save_file
+        save_file(dict(sd), os.path.join(path, "model.safetensors"))
+    elif fmt == "bin":
+        torch.save(dict(sd), os.path.join(path, "pytorch_model.bin"))
+    else:
+        raise ValueError("fmt must be 'safetensors' or 'bin'")
+    return path

@@ -12,8 +12,13 @@ Drop-in surface kept from the reference:
 
 CN-HuBERT runs on the device (hubert.py, loaded lazily from models_dir/chinese-hubert-base as TTS.py:111 does), and
 so do ERes2NetV2 with its 16 kHz resampling and Kaldi fbank (sv.py, from models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt,
-TTS.py:113).  What else sits in front of the hot path in the reference -- G2P text frontends, audio file decoding, the
-RoBERTa model -- is OUT OF SCOPE of this build (CPU string processing and third-party
+TTS.py:113) and Chinese RoBERTa (roberta.py, from models_dir/chinese-roberta-wwm-ext-large, TTS.py:112): use_bert=True
+loads it in __init__, auto_bert=True (the default) loads it on the first infer / infer_stream / infer_batched whose text
+holds a CJK ideograph (the reference asks LangSegment for "zh", which is not available here, so kanji-only Japanese
+text loads it too).  Either sets tts_config.cnroberta, so a frontend written as
+`lambda t: get_phones_and_bert(t, tts.tts_config)` gets device BERT features; without the directory one warning is
+logged and bert2 stays zeros.  What else sits in front of the hot path in the reference -- G2P text frontends and audio
+file decoding -- is OUT OF SCOPE of this build (CPU string processing and third-party
 packages not installable here).  Their *outputs* enter through the same caches the reference keeps:
     cache_spk_audio(path, ge=...)  or  cache_spk_audio(path, audio=<model-rate waveform>[, sv_emb=<ERes2Net embedding>])
                                    (spectrogram + get_ge on the device, and for v2Pro / v2ProPlus without sv_emb the
@@ -59,6 +64,7 @@ class Config:
         self.use_flash_attn = False
         self.gpt_cache = []
         self.sovits_cache = []
+        self.cnroberta = None   # Config.py:95: the BERT featurizer get_phones_and_bert calls (roberta.CNRobertaNative)
 
 
 class AudioClip:
@@ -164,6 +170,10 @@ class TTS:
         self.sv_path = Path(self.models_dir) / "sv" / "pretrained_eres2netv2w24s4ep4.ckpt"
         self.always_load_sv = always_load_sv
         self.sv_model = None
+        self.cnroberta_path = Path(self.models_dir) / "chinese-roberta-wwm-ext-large"
+        self.auto_bert = auto_bert
+        self._bert_loaded = False
+        self._bert_missing_warned = False
         self.gpt_models: dict = {}
         self.sovits_models: dict = {}
         self.spk_audio_cache: dict = {}
@@ -175,6 +185,8 @@ class TTS:
         # multi-GPU (one process per GPU): the rank on which infer_batched returns the clips; the other ranks return None.
         # None = every rank gets every clip (an all-gather of the audio instead of point-to-point sends to one rank)
         self.gather_dst = 0
+        if use_bert:
+            self._ensure_bert_loaded(force=True)
 
     # ------------------------------------------------------------------ model management
     def load_gpt_model(self, *model_paths):
@@ -384,6 +396,28 @@ class TTS:
             bert2 = torch.zeros(len(phones2), 1024)
         return list(phones2), word2ph, bert2.to(self.tts_config.device), norm_text
 
+    @staticmethod
+    def _contains_chinese(text: str) -> bool:
+        """TTS.py:1525-1531 asks LangSegment for a "zh" segment; here any CJK ideograph counts (kanji-only Japanese too)"""
+        return any(0x4E00 <= ord(c) <= 0x9FFF or 0x3400 <= ord(c) <= 0x4DBF or 0x20000 <= ord(c) <= 0x2FA1F or
+                   0xF900 <= ord(c) <= 0xFAFF for c in text)
+
+    def _ensure_bert_loaded(self, force: bool = False):
+        """TTS.py:1533-1551: load Chinese RoBERTa once and set tts_config.cnroberta.  There is no download: without the
+        directory one warning is logged and BERT features stay zeros, as before."""
+        if self._bert_loaded or not (force or self.auto_bert):
+            return
+        if not os.path.isdir(self.cnroberta_path):
+            if not self._bert_missing_warned:
+                log.warning("Chinese RoBERTa directory %s not found: BERT features stay zeros; install "
+                            "chinese-roberta-wwm-ext-large there to use them", self.cnroberta_path)
+                self._bert_missing_warned = True
+            return
+        from .roberta import load_cnroberta
+        self.tts_config.cnroberta = load_cnroberta(self.cnroberta_path, self.tts_config.device, self.tts_config.dtype)
+        self._bert_loaded = True
+        log.info("BERT model loaded for Chinese text")
+
     def _ge_for(self, spk_audio_path, sovits_model):
         def one(p):
             if p not in self.spk_audio_cache or sovits_model not in self.spk_audio_cache[p]["ge"]:
@@ -481,6 +515,8 @@ class TTS:
               sovits_model=None):
         with self._infer_lock:
             try:
+                if self._contains_chinese(text):
+                    self._ensure_bert_loaded()
                 if not self._check_pause(text):
                     text += "."
                 gpt_model = self._pick(self.gpt_models, gpt_model, self.default_gpt_path)
@@ -609,6 +645,8 @@ class TTS:
         to the previous one by SOLA over `overlap_len` frames."""
         with self._infer_lock:
             try:
+                if self._contains_chinese(text):
+                    self._ensure_bert_loaded()
                 if not self._check_pause(text):
                     text += "."
                 if stream_mode == "sentence":
@@ -700,6 +738,8 @@ class TTS:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
+                if any(self._contains_chinese(t) for t in texts):
+                    self._ensure_bert_loaded()
                 texts = [t if self._check_pause(t) else t + "." for t in texts]
                 if not is_cut_text:
                     cut_minlen = 10000

@@ -449,6 +449,43 @@ int gsv_sv_forward(gsv_sv* h, const float* feat, int n_frames, float* sv_emb, vo
 int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, float* sv_emb, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* Chinese RoBERTa, once per request: hidden_states[-3] of BertForMaskedLM (chinese-roberta-wwm-ext-large) and the
+ * phone features CNRoberta._forward_pytorch builds from them (gsv_tts/GPT_SoVITS/Featurizer/cnroberta.py), fp32 in every
+ * mode.  Absolute positions, exact GELU, post-LN layers; only encoder.layer.0 .. n_layer-3 run (hidden_states[-3] is
+ * their output; the embeddings' LayerNorm when n_layer == 2).  Tensors under their Hugging Face names without the
+ * "bert." prefix ("embeddings.*", "encoder.layer.{l}.*"), device fp32, before finalize; the last two layers, the pooler
+ * and cls.* are refused.  Texts run packed: ids int32 [total_rows] holds every text's [CLS] .. [SEP] ids back to back,
+ * seq_starts int32 [n_seq + 1] (device) delimits them, positions restart at every text and token type is 0.  A text's
+ * rows are bit-identical whatever else is in the batch, and two calls are bit-identical (no atomics). */
+typedef struct gsv_roberta gsv_roberta;
+typedef struct gsv_roberta_config {
+    int hidden;       /* hidden_size (1024); a multiple of 64, <= 1024, head dim hidden / n_head must be 64 */
+    int n_layer;      /* num_hidden_layers (24), >= 2; n_layer - 2 of them run */
+    int n_head;       /* num_attention_heads (16) */
+    int ffn;          /* intermediate_size (4096), a multiple of 64 */
+    int vocab;        /* vocab_size (21128) */
+    int max_pos;      /* max_position_embeddings (512): the longest text, [CLS] and [SEP] included */
+    int type_vocab;   /* type_vocab_size (2); row 0 is added */
+    float eps;        /* layer_norm_eps (1e-12) */
+} gsv_roberta_config;
+/* refuses (GSV_ERR_ARG, gsv_last_error says why) any shape the kernels do not support */
+int gsv_roberta_create(const gsv_roberta_config* cfg, gsv_roberta** out);
+int gsv_roberta_destroy(gsv_roberta* h);
+int gsv_roberta_load_tensor(gsv_roberta* h, const char* name, const float* data, int64_t numel, void* stream);
+int gsv_roberta_finalize(gsv_roberta* h, void* stream);
+/* device bytes of the caller-owned workspace of one call over total_rows packed rows of n_seq texts, the longest
+ * max_len rows; 0 on bad arguments */
+size_t gsv_roberta_workspace(gsv_roberta* h, int total_rows, int n_seq, int max_len);
+/* ids, seq_starts as above (2 <= every length <= max_len <= max_pos) -> hidden_out fp32 [total_rows][hidden] =
+ * hidden_states[-3] at every packed row.  Nothing is allocated. */
+int gsv_roberta_forward(gsv_roberta* h, const int* ids, const int* seq_starts, int n_seq, int total_rows, int max_len,
+                        float* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+/* the same forward, then out fp32 [n_phones][hidden] = hidden row phone_index[p] (int32, device): the host builds the
+ * index from word2ph["ph"], skipping every text's [CLS] and [SEP] rows and repeating the others. */
+int gsv_roberta_features(gsv_roberta* h, const int* ids, const int* seq_starts, int n_seq, int total_rows, int max_len,
+                         const int* phone_index, int n_phones, float* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
