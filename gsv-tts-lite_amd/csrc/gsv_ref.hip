@@ -20,6 +20,8 @@
 
 using namespace gsv;
 
+static_assert(AUX_MAX_CLIPS == GSV_AUX_MAX_CLIPS, "the kernels' per-clip argument arrays hold GSV_AUX_MAX_CLIPS clips");
+
 #define RCHK(expr)                                                                                        \
     do {                                                                                                  \
         hipError_t e_ = (expr);                                                                           \
@@ -318,12 +320,14 @@ bool hub_frames(const gsv_hubert_config& c, int n, int* T) {
 
 std::string hub_layer(int l, const char* rest) { return "encoder.layers." + std::to_string(l) + "." + rest; }
 
-// workspace carve-up of one forward, in floats (256-byte slots); the same walk sizes and assigns it
+// workspace carve-up of one forward, in floats (256-byte slots); the same walk sizes and assigns it.  T: the encoder
+// frames of the (longest) clip; rows / prows: the transformer rows and the padded positional-conv rows; feat_rows: rows of
+// a batch's packed encoder output (0 for one clip, whose encoder output stays in act)
 struct HubWs {
-    float *act[2], *pmean, *pm2, *gmean, *gscale, *hid, *pg, *part, *x, *tmp, *qkv, *att, *ffn;
+    float *act[2], *pmean, *pm2, *gmean, *gscale, *hid, *pg, *part, *x, *tmp, *qkv, *att, *ffn, *feat;
     size_t total;
 };
-HubWs hub_carve(const gsv_hubert_config& c, const int* T, float* base) {
+HubWs hub_carve(const gsv_hubert_config& c, const int* T, size_t rows, size_t prows, size_t feat_rows, float* base) {
     HubWs w;
     size_t off = 0;
     auto take = [&](size_t n) { float* r = base ? base + off : nullptr; off += up(n); return r; };
@@ -333,28 +337,143 @@ HubWs hub_carve(const gsv_hubert_config& c, const int* T, float* base) {
         a = std::max(a, (size_t)T[i] * c.conv_dim[i]);
     }
     const int C0 = c.conv_dim[0], nch = (T[0] + GN_ROWS - 1) / GN_ROWS;
-    const size_t Th = T[c.n_conv - 1], H = c.hidden;
+    const size_t H = c.hidden;
     w.act[0] = take(a0);
     w.act[1] = take(a1);
     w.pmean = take((size_t)nch * C0);
     w.pm2 = take((size_t)nch * C0);
     w.gmean = take(C0);
     w.gscale = take(C0);
-    w.hid = take(Th * H);
-    w.pg = take((Th + c.pos_k - 1) * H);
-    w.part = take(POS_SPLIT * Th * H);
-    w.x = take(Th * H);
-    w.tmp = take(Th * H);
-    w.qkv = take(Th * 3 * H);
-    w.att = take(Th * H);
-    w.ffn = take(Th * c.ffn);
+    w.hid = take(rows * H);
+    w.pg = take(prows * H);
+    w.part = take(POS_SPLIT * rows * H);
+    w.x = take(rows * H);
+    w.tmp = take(rows * H);
+    w.qkv = take(rows * 3 * H);
+    w.att = take(rows * H);
+    w.ffn = take(rows * c.ffn);
+    w.feat = take(feat_rows * c.conv_dim[c.n_conv - 1]);
     w.total = off;
     return w;
+}
+
+// one clip's carve-up
+HubWs hub_carve1(const gsv_hubert_config& c, const int* T, float* base) {
+    const size_t Th = T[c.n_conv - 1];
+    return hub_carve(c, T, Th, Th + c.pos_k - 1, 0, base);
+}
+
+// a batch: every clip's encoder frames, its first sample, and the packing of its rows
+struct HubBatch {
+    int n, longest;                                  // clips; the longest (the largest encoder buffers)
+    int T[GSV_AUX_MAX_CLIPS][GSV_HUBERT_MAX_CONV];
+    long long a0[GSV_AUX_MAX_CLIPS];
+    HubClips cl;
+    int rows, prows;                                 // packed transformer rows, padded positional-conv rows
+};
+// -1, or the index of the first clip too short for the feature encoder (n when the packed rows overflow)
+int hub_batch(const gsv_hubert_config& c, const int* ns, int n, HubBatch& b) {
+    b.n = n;
+    b.longest = 0;
+    b.cl.n = n;
+    long long a = 0, rows = 0, prows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!hub_frames(c, ns[i], b.T[i])) return i;
+        const int Th = b.T[i][c.n_conv - 1];
+        b.a0[i] = a;
+        b.cl.row0[i] = (int)rows;
+        b.cl.prow0[i] = (int)prows;
+        b.cl.T[i] = Th;
+        a += ns[i];
+        rows += Th;
+        prows += Th + c.pos_k - 1;
+        if (prows > 0x7fffffff) return n;
+        if (ns[i] > ns[b.longest]) b.longest = i;
+    }
+    b.rows = (int)rows;
+    b.prows = (int)prows;
+    return -1;
+}
+
+HubWs hub_carve_batch(const gsv_hubert_config& c, const HubBatch& b, float* base) {
+    return hub_carve(c, b.T[b.longest], b.rows, b.prows, b.rows, base);
 }
 
 int ln(hipStream_t st, const float* x, float* y, int rows, int C, const float* g, const float* b, float eps) {
     ln_rows_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, y, rows, C, g, b, eps);
     return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// feature encoder of one clip: conv 0 as rows of k0 samples at stride s0 over the waveform, GroupNorm(C0, C0) over the
+// clip's T0 frames + GELU, then convs 1.. (rows of k * cin values at stride s * cin over the channels-last activations,
+// GELU epilogue).  The last conv writes out [T_last][C_last], the others ping-pong through w.act.
+int hub_encoder(gsv_hubert* h, hipStream_t st, const float* audio, const int* T, const HubWs& w, float* out) {
+    const gsv_hubert_config& c = h->cfg;
+    const int C0 = c.conv_dim[0];
+    auto dst = [&](int i) { return i == c.n_conv - 1 ? out : w.act[i & 1]; };
+    int bad = fgemm(st, audio, c.conv_stride[0], HT(h, "feature_extractor.conv_layers.0.conv.weight"), c.conv_kernel[0], dst(0),
+                    C0, T[0], C0, c.conv_kernel[0]);
+    const int nch = (T[0] + GN_ROWS - 1) / GN_ROWS;
+    gn_partial_kernel<<<dim3(C0 / 64, nch), 256, 0, st>>>(dst(0), T[0], C0, w.pmean, w.pm2);
+    gn_finalize_kernel<<<(C0 + 255) / 256, 256, 0, st>>>(w.pmean, w.pm2, nch, T[0], C0, HT(h, "feature_extractor.conv_layers.0.layer_norm.weight"),
+                                                        1e-5f, w.gmean, w.gscale);
+    const long long n4 = (long long)T[0] * C0 / 4;
+    gn_apply_gelu_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(dst(0), n4, C0, w.gmean, w.gscale,
+                                                                       HT(h, "feature_extractor.conv_layers.0.layer_norm.bias"));
+    for (int i = 1; i < c.n_conv; ++i) {
+        const int ci = c.conv_dim[i - 1], co = c.conv_dim[i];
+        bad |= fgemm(st, dst(i - 1), (long long)c.conv_stride[i] * ci, h->w_conv[i], (long long)c.conv_kernel[i] * ci, dst(i), co,
+                     T[i], co, c.conv_kernel[i] * ci, nullptr, 2);
+    }
+    return bad;
+}
+
+// everything after the encoder, over `rows` packed rows of feat [rows][C_last] -> w.x [rows][H]: cl null for one clip
+// (the single-clip kernels), else the clips it describes (prows padded rows in w.pg)
+int hub_body(gsv_hubert* h, hipStream_t st, const HubWs& w, float* feat, int rows, const HubClips* cl, int prows) {
+    const gsv_hubert_config& c = h->cfg;
+    const int H = c.hidden, CL = c.conv_dim[c.n_conv - 1];
+    const int G = c.pos_groups, cg = H / G, K = c.pos_k;
+    int tmax = rows;   // the longest clip's frames
+    if (cl) {
+        tmax = 0;
+        for (int z = 0; z < cl->n; ++z) tmax = std::max(tmax, cl->T[z]);
+    }
+    int bad = 0;
+    // feature projection: LayerNorm(CL) in place, Linear CL -> H
+    bad |= ln(st, feat, feat, rows, CL, HT(h, "feature_projection.layer_norm.weight"), HT(h, "feature_projection.layer_norm.bias"), c.eps);
+    bad |= fgemm(st, feat, CL, HT(h, "feature_projection.projection.weight"), CL, w.hid, H, rows, H, CL, HT(h, "feature_projection.projection.bias"));
+    // positional conv over the group-major padded copy: tmp = hid + gelu(conv(hid) + bias), the last frame never made
+    {
+        const long long np = (long long)G * (tmax + K - 1) * cg, n = (long long)rows * H;
+        if (!cl) {
+            pos_pad_group_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w.hid, rows, H, G, K, w.pg);
+            pos_conv_split_kernel<<<dim3((cg + 63) / 64, (rows + 63) / 64, G * POS_SPLIT), 256, 0, st>>>(w.pg, h->w_pos, w.part, rows, H, G, K);
+        } else {
+            pos_pad_group_batch_kernel<<<dim3((unsigned)((np + 255) / 256), cl->n), 256, 0, st>>>(w.hid, H, G, K, prows, *cl, w.pg);
+            pos_conv_split_batch_kernel<<<dim3((cg + 63) / 64 * cl->n, (tmax + 63) / 64, G * POS_SPLIT), 256, 0, st>>>(
+                w.pg, prows, h->w_pos, w.part, rows, H, G, K, *cl);
+        }
+        pos_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.part, n, H, HT(h, "encoder.pos_conv_embed.conv.bias"), w.hid, w.tmp);
+    }
+    bad |= ln(st, w.tmp, w.x, rows, H, HT(h, "encoder.layer_norm.weight"), HT(h, "encoder.layer_norm.bias"), c.eps);
+    const float scale = 1.f / sqrtf(64.f);
+    for (int l = 0; l < c.n_layer; ++l) {
+        bad |= fgemm(st, w.x, H, h->w_qkv[l], H, w.qkv, 3 * H, rows, 3 * H, H, h->b_qkv[l]);
+        if (!cl)
+            hubert_attn_kernel<<<dim3((rows + ATT_QB - 1) / ATT_QB, c.n_head), 128, 0, st>>>(w.qkv, 3 * H, rows, H, scale, w.att, H);
+        else
+            hubert_attn_batch_kernel<<<dim3((tmax + ATT_QB - 1) / ATT_QB, c.n_head, cl->n), 128, 0, st>>>(w.qkv, 3 * H, H, scale, w.att, H, *cl);
+        bad |= fgemm(st, w.att, H, HT(h, hub_layer(l, "attention.out_proj.weight")), H, w.tmp, H, rows, H, H,
+                     HT(h, hub_layer(l, "attention.out_proj.bias")), 0, w.x, H);
+        bad |= ln(st, w.tmp, w.x, rows, H, HT(h, hub_layer(l, "layer_norm.weight")), HT(h, hub_layer(l, "layer_norm.bias")), c.eps);
+        bad |= fgemm(st, w.x, H, HT(h, hub_layer(l, "feed_forward.intermediate_dense.weight")), H, w.ffn, c.ffn, rows, c.ffn, H,
+                     HT(h, hub_layer(l, "feed_forward.intermediate_dense.bias")), 2);
+        bad |= fgemm(st, w.ffn, c.ffn, HT(h, hub_layer(l, "feed_forward.output_dense.weight")), c.ffn, w.tmp, H, rows, H, c.ffn,
+                     HT(h, hub_layer(l, "feed_forward.output_dense.bias")), 0, w.x, H);
+        bad |= ln(st, w.tmp, w.x, rows, H, HT(h, hub_layer(l, "final_layer_norm.weight")), HT(h, hub_layer(l, "final_layer_norm.bias")), c.eps);
+    }
+    return bad;
 }
 
 }  // namespace
@@ -486,7 +605,7 @@ size_t gsv_hubert_workspace(gsv_hubert* h, int n_samples) {
     if (!h) return 0;
     int T[GSV_HUBERT_MAX_CONV];
     if (!hub_frames(h->cfg, n_samples, T)) return 0;
-    return sizeof(float) * hub_carve(h->cfg, T, nullptr).total;
+    return sizeof(float) * hub_carve1(h->cfg, T, nullptr).total;
 }
 
 int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* ssl, void* workspace, size_t workspace_bytes,
@@ -499,54 +618,52 @@ int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* 
     if (workspace_bytes < gsv_hubert_workspace(h, n_samples)) return abi_fail(GSV_ERR_ARG, "hubert: workspace too small");
     if ((reinterpret_cast<size_t>(workspace) & 15) != 0) return abi_fail(GSV_ERR_ARG, "hubert: workspace must be 16-byte aligned");
     hipStream_t st = S(stream);
-    const HubWs w = hub_carve(c, T, static_cast<float*>(workspace));
-    const int H = c.hidden, Th = T[c.n_conv - 1], C0 = c.conv_dim[0], CL = c.conv_dim[c.n_conv - 1];
-    const int G = c.pos_groups, cg = H / G, K = c.pos_k, Tp = Th + K - 1;
-    int bad = 0;
-    // conv 0: rows of k0 samples at stride s0 over the waveform, then GroupNorm(C0, C0) over all T0 frames + GELU
-    bad |= fgemm(st, audio, c.conv_stride[0], HT(h, "feature_extractor.conv_layers.0.conv.weight"), c.conv_kernel[0], w.act[0], C0,
-                 T[0], C0, c.conv_kernel[0]);
-    const int nch = (T[0] + GN_ROWS - 1) / GN_ROWS;
-    gn_partial_kernel<<<dim3(C0 / 64, nch), 256, 0, st>>>(w.act[0], T[0], C0, w.pmean, w.pm2);
-    gn_finalize_kernel<<<(C0 + 255) / 256, 256, 0, st>>>(w.pmean, w.pm2, nch, T[0], C0, HT(h, "feature_extractor.conv_layers.0.layer_norm.weight"),
-                                                        1e-5f, w.gmean, w.gscale);
-    const long long n4 = (long long)T[0] * C0 / 4;
-    gn_apply_gelu_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, st>>>(w.act[0], n4, C0, w.gmean, w.gscale,
-                                                                       HT(h, "feature_extractor.conv_layers.0.layer_norm.bias"));
-    // convs 1..: rows of k * cin values at stride s * cin over the channels-last activations, GELU epilogue
-    for (int i = 1; i < c.n_conv; ++i) {
-        const int ci = c.conv_dim[i - 1], co = c.conv_dim[i];
-        bad |= fgemm(st, w.act[(i - 1) & 1], (long long)c.conv_stride[i] * ci, h->w_conv[i], (long long)c.conv_kernel[i] * ci,
-                     w.act[i & 1], co, T[i], co, c.conv_kernel[i] * ci, nullptr, 2);
-    }
+    const HubWs w = hub_carve1(c, T, static_cast<float*>(workspace));
+    const int H = c.hidden, Th = T[c.n_conv - 1];
     float* feat = w.act[(c.n_conv - 1) & 1];
-    // feature projection: LayerNorm(CL) in place, Linear CL -> H
-    bad |= ln(st, feat, feat, Th, CL, HT(h, "feature_projection.layer_norm.weight"), HT(h, "feature_projection.layer_norm.bias"), c.eps);
-    bad |= fgemm(st, feat, CL, HT(h, "feature_projection.projection.weight"), CL, w.hid, H, Th, H, CL, HT(h, "feature_projection.projection.bias"));
-    // positional conv over the group-major padded copy: tmp = hid + gelu(conv(hid) + bias), the last frame never made
-    {
-        const long long np = (long long)G * Tp * cg, n = (long long)Th * H;
-        pos_pad_group_kernel<<<(unsigned)((np + 255) / 256), 256, 0, st>>>(w.hid, Th, H, G, K, w.pg);
-        pos_conv_split_kernel<<<dim3((cg + 63) / 64, (Th + 63) / 64, G * POS_SPLIT), 256, 0, st>>>(w.pg, h->w_pos, w.part, Th, H, G, K);
-        pos_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(w.part, n, H, HT(h, "encoder.pos_conv_embed.conv.bias"), w.hid, w.tmp);
-    }
-    bad |= ln(st, w.tmp, w.x, Th, H, HT(h, "encoder.layer_norm.weight"), HT(h, "encoder.layer_norm.bias"), c.eps);
-    const float scale = 1.f / sqrtf(64.f);
-    for (int l = 0; l < c.n_layer; ++l) {
-        bad |= fgemm(st, w.x, H, h->w_qkv[l], H, w.qkv, 3 * H, Th, 3 * H, H, h->b_qkv[l]);
-        hubert_attn_kernel<<<dim3((Th + ATT_QB - 1) / ATT_QB, c.n_head), 128, 0, st>>>(w.qkv, 3 * H, Th, H, scale, w.att, H);
-        bad |= fgemm(st, w.att, H, HT(h, hub_layer(l, "attention.out_proj.weight")), H, w.tmp, H, Th, H, H,
-                     HT(h, hub_layer(l, "attention.out_proj.bias")), 0, w.x, H);
-        bad |= ln(st, w.tmp, w.x, Th, H, HT(h, hub_layer(l, "layer_norm.weight")), HT(h, hub_layer(l, "layer_norm.bias")), c.eps);
-        bad |= fgemm(st, w.x, H, HT(h, hub_layer(l, "feed_forward.intermediate_dense.weight")), H, w.ffn, c.ffn, Th, c.ffn, H,
-                     HT(h, hub_layer(l, "feed_forward.intermediate_dense.bias")), 2);
-        bad |= fgemm(st, w.ffn, c.ffn, HT(h, hub_layer(l, "feed_forward.output_dense.weight")), c.ffn, w.tmp, H, Th, H, c.ffn,
-                     HT(h, hub_layer(l, "feed_forward.output_dense.bias")), 0, w.x, H);
-        bad |= ln(st, w.tmp, w.x, Th, H, HT(h, hub_layer(l, "final_layer_norm.weight")), HT(h, hub_layer(l, "final_layer_norm.bias")), c.eps);
-    }
+    int bad = hub_encoder(h, st, audio, T, w, feat);
+    bad |= hub_body(h, st, w, feat, Th, nullptr, 0);
     // [Th][H] -> ssl [H][Th]
     transpose_kernel<<<dim3((H + 31) / 32, (Th + 31) / 32), 256, 0, st>>>(w.x, H, ssl, Th, Th, H);
     if (bad) return abi_fail(GSV_ERR_HIP, "hubert: a forward launch failed");
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+size_t gsv_hubert_batch_workspace(gsv_hubert* h, const int* n_samples, int n_clips) {
+    if (!h || !n_samples || n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS) return 0;
+    HubBatch b;
+    if (hub_batch(h->cfg, n_samples, n_clips, b) >= 0) return 0;
+    return sizeof(float) * hub_carve_batch(h->cfg, b, nullptr).total;
+}
+
+int gsv_hubert_forward_batch(gsv_hubert* h, const float* audio, const int* n_samples, int n_clips, float* ssl, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (!h || !audio || !n_samples || !ssl || !workspace) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (!h->finalized) return abi_fail(GSV_ERR_STATE, "hubert: not finalized");
+    if (n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS) return abi_fail(GSV_ERR_ARG, "hubert: %d clips (1..%d per call)", n_clips, GSV_AUX_MAX_CLIPS);
+    const gsv_hubert_config& c = h->cfg;
+    HubBatch b;
+    const int badc = hub_batch(c, n_samples, n_clips, b);
+    if (badc == n_clips) return abi_fail(GSV_ERR_ARG, "hubert: the batch's packed frames overflow");
+    if (badc >= 0)
+        return abi_fail(GSV_ERR_ARG, "hubert: clip %d: %d samples are too short for the feature encoder", badc, n_samples[badc]);
+    if (workspace_bytes < sizeof(float) * hub_carve_batch(c, b, nullptr).total) return abi_fail(GSV_ERR_ARG, "hubert: workspace too small");
+    if ((reinterpret_cast<size_t>(workspace) & 15) != 0) return abi_fail(GSV_ERR_ARG, "hubert: workspace must be 16-byte aligned");
+    hipStream_t st = S(stream);
+    const HubWs w = hub_carve_batch(c, b, static_cast<float*>(workspace));
+    const int H = c.hidden, CL = c.conv_dim[c.n_conv - 1];
+    int bad = 0;
+    // the encoder per clip (its GroupNorm statistics are the clip's own), each into its rows of the packed feat
+    for (int i = 0; i < n_clips; ++i) bad |= hub_encoder(h, st, audio + b.a0[i], b.T[i], w, w.feat + (long long)b.cl.row0[i] * CL);
+    bad |= hub_body(h, st, w, w.feat, b.rows, &b.cl, b.prows);
+    // clip i's rows [Th_i][H] -> its ssl block [H][Th_i] at H * row0
+    for (int i = 0; i < n_clips; ++i) {
+        const int Th = b.cl.T[i];
+        const long long r0 = b.cl.row0[i];
+        transpose_kernel<<<dim3((H + 31) / 32, (Th + 31) / 32), 256, 0, st>>>(w.x + r0 * H, H, ssl + r0 * H, Th, Th, H);
+    }
+    if (bad) return abi_fail(GSV_ERR_HIP, "hubert: a batched forward launch failed");
     RCHK(hipGetLastError());
     return GSV_OK;
 }
@@ -609,7 +726,39 @@ SvGeo sv_geo(const gsv_sv_config& c, int T) {
     return g;
 }
 
-// workspace of one embed: resample table and output, fbank buffers, then the model's zero-padded activations
+// the clips of one forward3 (one for the single-clip calls): every clip's frames and the pixel offset of its padded
+// [F + 2][T + 2] image at each stage geometry ("level" s: stage s; level 0 is also the stem's), and its first fbank row
+struct SvBatch {
+    int n;
+    int F[4];
+    int T[4][GSV_AUX_MAX_CLIPS];
+    long long off[4][GSV_AUX_MAX_CLIPS];
+    size_t px[4];                          // pixels of all clips' images at each level
+    int feat0[GSV_AUX_MAX_CLIPS];
+    size_t rows;                           // fbank rows of all clips
+};
+SvBatch sv_batch(const gsv_sv_config& c, const int* T, int n) {
+    SvBatch b;
+    b.n = n;
+    b.rows = 0;
+    for (int s = 0; s < 4; ++s) b.px[s] = 0;
+    for (int i = 0; i < n; ++i) {
+        const SvGeo g = sv_geo(c, T[i]);
+        for (int s = 0; s < 4; ++s) {
+            b.F[s] = g.F[s];
+            b.T[s][i] = g.T[s];
+            b.off[s][i] = (long long)b.px[s];
+            b.px[s] += (size_t)(g.F[s] + 2) * (g.T[s] + 2);
+        }
+        b.feat0[i] = (int)b.rows;
+        b.rows += T[i];
+    }
+    return b;
+}
+
+// workspace of one embed: resample table and output, fbank buffers, then the model's zero-padded activations.  A batch
+// (n_max: its longest clip, whose buffers the per-clip resample / fbank reuse) keeps every clip's fbank rows and every
+// clip's images of each model buffer back to back.
 struct SvWs {
     float *tab, *y16, *fr, *Z, *P, *E, *feat;
     float *model;                          // start of the zero-filled model region
@@ -618,13 +767,13 @@ struct SvWs {
     float *ds, *h34, *fuse;
     size_t model_floats, total;
 };
-SvWs sv_carve(const gsv_sv_config& c, long long n, int sr, float* base) {
+SvWs sv_carve_batch(const gsv_sv_config& c, long long n_max, int sr, const SvBatch& b, float* base) {
     SvWs w;
     size_t off = 0;
     auto take = [&](size_t k) { float* r = base ? base + off : nullptr; off += up(k); return r; };
     int o = 1, nw = 1, width = 0;
     rs_params(sr, 16000, &o, &nw, &width);
-    const long long n16 = rs_length(n, sr, 16000);
+    const long long n16 = rs_length(n_max, sr, 16000);
     const int T = fb_frames(n16);
     w.tab = take(o == nw ? 0 : (size_t)nw * (2 * width + o));
     w.y16 = take(sr == 16000 ? 0 : (size_t)n16);
@@ -632,16 +781,14 @@ SvWs sv_carve(const gsv_sv_config& c, long long n, int sr, float* base) {
     w.Z = take((size_t)T * 2 * FB_BINS);
     w.P = take((size_t)T * FB_BINS);
     w.E = take((size_t)T * FB_MELS);
-    w.feat = take((size_t)T * FB_MELS);
+    w.feat = take(b.rows * FB_MELS);
     const size_t m0 = off;
     w.model = base ? base + off : nullptr;
-    const SvGeo g = sv_geo(c, T);
     const int m = c.m_channels;
-    auto pix = [](int F, int Tt) { return (size_t)(F + 2) * (Tt + 2); };
-    w.in0 = take(pix(c.feat_dim, T));
-    w.stem = take(pix(c.feat_dim, T) * m);
+    w.in0 = take(b.px[0]);
+    w.stem = take(b.px[0] * m);
     for (int s = 0; s < 4; ++s) {
-        const size_t p = pix(g.F[s], g.T[s]);
+        const size_t p = b.px[s];
         const int C = 4 * (m << s), wd = c.width[s];
         w.x[s][0] = take(p * C);
         w.x[s][1] = take(p * C);
@@ -650,13 +797,19 @@ SvWs sv_carve(const gsv_sv_config& c, long long n, int sr, float* base) {
         w.hh[s] = s >= 2 ? take(p * (wd / 4)) : nullptr;
         w.fu[s] = s >= 2 ? take(p * wd) : nullptr;
     }
-    const size_t p4 = pix(g.F[3], g.T[3]);
+    const size_t p4 = b.px[3];
     w.ds = take(p4 * 32 * m);
     w.h34 = take(p4 * 8 * m);
     w.fuse = take(p4 * 32 * m);
     w.model_floats = off - m0;
     w.total = off;
     return w;
+}
+
+// one clip of n samples at sr
+SvWs sv_carve(const gsv_sv_config& c, long long n, int sr, float* base) {
+    const int T = fb_frames(rs_length(n, sr, 16000));
+    return sv_carve_batch(c, n, sr, sv_batch(c, &T, 1), base);
 }
 
 std::string sv_blk(int s, int b, const char* rest) {
@@ -699,26 +852,46 @@ std::vector<SvConvSpec> sv_specs(const gsv_sv_config& c) {
     return v;
 }
 
-// one conv over padded channels-last buffers: input geometry (Fi, Ti), output (Fi - 1) / s + 1 x (Ti - 1) / s + 1
+// one conv over padded channels-last buffers: input at level lin (geometry F[lin] x T[lin][clip]), output at level lin
+// (stride 1) or lin + 1 (stride 2: (Fi - 1) / 2 + 1 x (Ti - 1) / 2 + 1); one clip runs sv_conv_kernel, a batch
+// sv_conv_batch_kernel with a clip grid dimension
 struct SvIO {
     const float* x1; const float* x2; int src, ldx;
     float* y; int ldy;
     const float* r = nullptr; int ldr = 0;
     const float* a = nullptr; int lda = 0; const float* b = nullptr; int ldb = 0;
 };
-int sv_conv(hipStream_t st, const gsv_sv::Conv& cw, int stride, int Fi, int Ti, const SvIO& io, int act) {
+int sv_conv(hipStream_t st, const gsv_sv::Conv& cw, int stride, const SvBatch& B, int lin, const SvIO& io, int act) {
+    const int Fi = B.F[lin], lout = stride == 1 ? lin : lin + 1;
     SvConvArgs a;
-    a.X1 = io.x1; a.X2 = io.x2; a.src = io.src; a.ldx = io.ldx; a.Tpi = Ti + 2;
+    a.X1 = io.x1; a.X2 = io.x2; a.src = io.src; a.ldx = io.ldx; a.Tpi = B.T[lin][0] + 2;
     a.Cin = io.src == SV_SRC_CAT ? cw.cin / 2 : cw.cin;
     a.k = cw.k; a.s = stride; a.W = cw.w; a.bias = cw.b;
     a.Y = io.y; a.ldy = io.ldy;
-    a.Fo = (Fi - 1) / stride + 1; a.To = (Ti - 1) / stride + 1; a.N = cw.cout;
+    a.Fo = (Fi - 1) / stride + 1; a.To = (B.T[lin][0] - 1) / stride + 1; a.N = cw.cout;
     a.R = io.r; a.ldr = io.ldr; a.A = io.a; a.lda = io.lda; a.B = io.b; a.ldb = io.ldb; a.act = act;
-    const long long M = (long long)a.Fo * a.To;
+    if (B.n == 1) {
+        const long long M = (long long)a.Fo * a.To;
+        if (a.N <= 32)
+            sv_conv_kernel<4, 1><<<dim3((a.N + 31) / 32, (unsigned)((M + 127) / 128)), 256, 0, st>>>(a);
+        else
+            sv_conv_kernel<2, 2><<<dim3((a.N + 63) / 64, (unsigned)((M + 63) / 64)), 256, 0, st>>>(a);
+        return hipGetLastError() == hipSuccess ? 0 : 1;
+    }
+    SvClips cl;
+    int tmax = 0;
+    for (int z = 0; z < B.n; ++z) {
+        cl.in_off[z] = B.off[lin][z];
+        cl.out_off[z] = B.off[lout][z];
+        cl.Ti[z] = B.T[lin][z];
+        cl.To[z] = B.T[lout][z];
+        tmax = std::max(tmax, cl.To[z]);
+    }
+    const long long M = (long long)a.Fo * tmax;
     if (a.N <= 32)
-        sv_conv_kernel<4, 1><<<dim3((a.N + 31) / 32, (unsigned)((M + 127) / 128)), 256, 0, st>>>(a);
+        sv_conv_batch_kernel<4, 1><<<dim3((a.N + 31) / 32, (unsigned)((M + 127) / 128), B.n), 256, 0, st>>>(a, cl);
     else
-        sv_conv_kernel<2, 2><<<dim3((a.N + 63) / 64, (unsigned)((M + 63) / 64)), 256, 0, st>>>(a);
+        sv_conv_batch_kernel<2, 2><<<dim3((a.N + 63) / 64, (unsigned)((M + 63) / 64), B.n), 256, 0, st>>>(a, cl);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
@@ -749,35 +922,36 @@ int sv_fbank_run(gsv_sv* h, hipStream_t st, const float* x16, int T, float* feat
     return GSV_OK;
 }
 
-int sv_forward_run(gsv_sv* h, hipStream_t st, const float* feat, int T, float* emb, const SvWs& w) {
+int sv_forward_run(gsv_sv* h, hipStream_t st, const float* feat, const SvBatch& B, float* emb, const SvWs& w) {
     const gsv_sv_config& c = h->cfg;
-    const SvGeo g = sv_geo(c, T);
     const int m = c.m_channels, F = c.feat_dim;
     auto CW = [&](const std::string& k) -> const gsv_sv::Conv& { return h->conv.at(k); };
     RCHK(hipMemsetAsync(w.model, 0, w.model_floats * sizeof(float), st));
-    const long long nf = (long long)T * F;
-    sv_feat_pad_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, st>>>(feat, T, F, w.in0);
+    for (int i = 0; i < B.n; ++i) {
+        const int T = B.T[0][i];
+        const long long nf = (long long)T * F;
+        sv_feat_pad_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, st>>>(feat + (long long)B.feat0[i] * F, T, F, w.in0 + B.off[0][i]);
+    }
     int bad = 0;
     {
         SvIO io{w.in0, nullptr, SV_SRC_ONE, 1, w.stem, m};
-        bad |= sv_conv(st, CW("conv1"), 1, F, T, io, SV_ACT_RELU);   // F.relu(bn1(conv1(x)))
+        bad |= sv_conv(st, CW("conv1"), 1, B, 0, io, SV_ACT_RELU);   // F.relu(bn1(conv1(x)))
     }
     const float* prev = w.stem;
-    int in = m, Fi = F, Ti = T;
+    int in = m;
     for (int s = 0; s < 4; ++s) {
         const int C = 4 * (m << s), wd = c.width[s], W4 = 4 * wd;
-        const int Fo = g.F[s], To = g.T[s];
         for (int b = 0; b < c.blocks[s]; ++b) {
             const int stride = (b == 0 && s > 0) ? 2 : 1;
             const float* X = b == 0 ? prev : w.x[s][(b - 1) & 1];
-            const int fi = b == 0 ? Fi : Fo, ti = b == 0 ? Ti : To;
+            const int lin = stride == 2 ? s - 1 : s;   // the block's input level
             float* Y = w.x[s][b & 1];
             SvIO i1{X, nullptr, SV_SRC_ONE, in, w.c1[s], W4};
-            bad |= sv_conv(st, CW(sv_blk(s, b, "conv1")), stride, fi, ti, i1, SV_ACT_HTANH);
+            bad |= sv_conv(st, CW(sv_blk(s, b, "conv1")), stride, B, lin, i1, SV_ACT_HTANH);
             const float* R = X;
             if (stride != 1 || in != C) {
                 SvIO isc{X, nullptr, SV_SRC_ONE, in, w.x[s][1], C};   // block 0 only: its output is x[s][0]
-                bad |= sv_conv(st, CW(sv_blk(s, b, "shortcut")), stride, fi, ti, isc, SV_ACT_NONE);
+                bad |= sv_conv(st, CW(sv_blk(s, b, "shortcut")), stride, B, lin, isc, SV_ACT_NONE);
                 R = w.x[s][1];
             }
             for (int i = 0; i < 4; ++i) {
@@ -789,41 +963,42 @@ int sv_forward_run(gsv_sv* h, hipStream_t st, const float* feat, int T, float* e
                 } else if (i > 0) {              // sp = AFF(sp, spx[i])
                     const std::string f = "fuse_models." + std::to_string(i - 1) + ".local_att.";
                     SvIO ih{w.cat[s] + (i - 1) * wd, w.c1[s] + i * wd, SV_SRC_CAT, W4, w.hh[s], wd / 4};
-                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "0").c_str())), 1, Fo, To, ih, SV_ACT_SILU);
+                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "0").c_str())), 1, B, s, ih, SV_ACT_SILU);
                     SvIO ia{w.hh[s], nullptr, SV_SRC_ONE, wd / 4, w.fu[s], wd};
                     ia.a = w.cat[s] + (i - 1) * wd; ia.lda = W4;
                     ia.b = w.c1[s] + i * wd; ia.ldb = W4;
-                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "3").c_str())), 1, Fo, To, ia, SV_ACT_AFF);
+                    bad |= sv_conv(st, CW(sv_blk(s, b, (f + "3").c_str())), 1, B, s, ia, SV_ACT_AFF);
                     ic.x1 = w.fu[s];
                     ic.ldx = wd;
                 } else {
                     ic.x1 = w.c1[s];
                 }
-                bad |= sv_conv(st, CW(sv_blk(s, b, ("convs." + std::to_string(i)).c_str())), 1, Fo, To, ic, SV_ACT_HTANH);
+                bad |= sv_conv(st, CW(sv_blk(s, b, ("convs." + std::to_string(i)).c_str())), 1, B, s, ic, SV_ACT_HTANH);
             }
             SvIO i3{w.cat[s], nullptr, SV_SRC_ONE, W4, Y, C};
             i3.r = R;
             i3.ldr = C;
-            bad |= sv_conv(st, CW(sv_blk(s, b, "conv3")), 1, Fo, To, i3, SV_ACT_HTANH);
+            bad |= sv_conv(st, CW(sv_blk(s, b, "conv3")), 1, B, s, i3, SV_ACT_HTANH);
             in = C;
         }
         prev = w.x[s][(c.blocks[s] - 1) & 1];
-        Fi = Fo;
-        Ti = To;
     }
     const float* out3 = w.x[2][(c.blocks[2] - 1) & 1];
     const float* out4 = prev;
-    const int C4 = 32 * m;
+    const int C4 = 32 * m, F3 = B.F[3];
     {
         SvIO ids{out3, nullptr, SV_SRC_ONE, 16 * m, w.ds, C4};
-        bad |= sv_conv(st, CW("layer3_ds"), 2, g.F[2], g.T[2], ids, SV_ACT_NONE);
+        bad |= sv_conv(st, CW("layer3_ds"), 2, B, 2, ids, SV_ACT_NONE);
         SvIO ih{out4, w.ds, SV_SRC_CAT, C4, w.h34, 8 * m};
-        bad |= sv_conv(st, CW("fuse34.0"), 1, g.F[3], g.T[3], ih, SV_ACT_SILU);
+        bad |= sv_conv(st, CW("fuse34.0"), 1, B, 3, ih, SV_ACT_SILU);
         SvIO ia{w.h34, nullptr, SV_SRC_ONE, 8 * m, w.fuse, C4};
         ia.a = out4; ia.lda = C4; ia.b = w.ds; ia.ldb = C4;
-        bad |= sv_conv(st, CW("fuse34.3"), 1, g.F[3], g.T[3], ia, SV_ACT_AFF);
+        bad |= sv_conv(st, CW("fuse34.3"), 1, B, 3, ia, SV_ACT_AFF);
     }
-    sv_mean_kernel<<<(g.F[3] * C4 + 255) / 256, 256, 0, st>>>(w.fuse, g.F[3], g.T[3], C4, emb);
+    // clip i's time mean -> emb[i] (emb_dim = C4 * F3)
+    for (int i = 0; i < B.n; ++i)
+        sv_mean_kernel<<<(F3 * C4 + 255) / 256, 256, 0, st>>>(w.fuse + B.off[3][i] * C4, F3, B.T[3][i], C4,
+                                                              emb + (long long)i * C4 * F3);
     if (bad) return abi_fail(GSV_ERR_HIP, "sv: a forward launch failed");
     RCHK(hipGetLastError());
     return GSV_OK;
@@ -833,6 +1008,38 @@ int sv_check_ws(gsv_sv* h, long long n, int sr, void* ws, size_t bytes) {
     if (!h->finalized) return abi_fail(GSV_ERR_STATE, "sv: not finalized");
     if (!ws) return abi_fail(GSV_ERR_ARG, "null argument");
     if (bytes < sizeof(float) * sv_carve(h->cfg, n, sr, nullptr).total) return abi_fail(GSV_ERR_ARG, "sv: workspace too small");
+    if ((reinterpret_cast<size_t>(ws) & 15) != 0) return abi_fail(GSV_ERR_ARG, "sv: workspace must be 16-byte aligned");
+    return GSV_OK;
+}
+
+// a batch's fbank frames per clip and its longest clip (in samples), from host sample counts at sr
+struct SvBatchIn {
+    int T[GSV_AUX_MAX_CLIPS];
+    long long n_max;
+};
+int sv_batch_in(const int* ns, int n, int sr, SvBatchIn& in) {
+    if (!ns) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (n < 1 || n > GSV_AUX_MAX_CLIPS) return abi_fail(GSV_ERR_ARG, "sv: %d clips (1..%d per call)", n, GSV_AUX_MAX_CLIPS);
+    int o, nw, width;
+    if (!rs_params(sr, 16000, &o, &nw, &width)) return abi_fail(GSV_ERR_ARG, "sv: sample rate %d unsupported", sr);
+    in.n_max = 0;
+    for (int i = 0; i < n; ++i) {
+        const long long n16 = rs_length(ns[i], sr, 16000);
+        in.T[i] = n16 < 0 ? 0 : fb_frames(n16);
+        if (in.T[i] < 1)
+            return abi_fail(GSV_ERR_ARG, "sv: clip %d: %d samples at %d Hz are too short for one fbank frame", i, ns[i], sr);
+        in.n_max = std::max(in.n_max, (long long)ns[i]);
+    }
+    return GSV_OK;
+}
+
+int sv_check_batch(gsv_sv* h, const int* ns, int n, int sr, void* ws, size_t bytes, SvBatchIn& in) {
+    if (!h->finalized) return abi_fail(GSV_ERR_STATE, "sv: not finalized");
+    int rc;
+    if ((rc = sv_batch_in(ns, n, sr, in))) return rc;
+    if (!ws) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (bytes < sizeof(float) * sv_carve_batch(h->cfg, in.n_max, sr, sv_batch(h->cfg, in.T, n), nullptr).total)
+        return abi_fail(GSV_ERR_ARG, "sv: workspace too small");
     if ((reinterpret_cast<size_t>(ws) & 15) != 0) return abi_fail(GSV_ERR_ARG, "sv: workspace must be 16-byte aligned");
     return GSV_OK;
 }
@@ -978,7 +1185,7 @@ int gsv_sv_forward(gsv_sv* h, const float* feat, int n_frames, float* sv_emb, vo
     int rc;
     if ((rc = sv_check_ws(h, n16, 16000, workspace, workspace_bytes))) return rc;
     const SvWs w = sv_carve(h->cfg, n16, 16000, static_cast<float*>(workspace));
-    return sv_forward_run(h, S(stream), feat, n_frames, sv_emb, w);
+    return sv_forward_run(h, S(stream), feat, sv_batch(h->cfg, &n_frames, 1), sv_emb, w);
 }
 
 int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, float* sv_emb, void* workspace, size_t workspace_bytes,
@@ -998,7 +1205,55 @@ int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, fl
         x16 = w.y16;
     }
     if ((rc = sv_fbank_run(h, st, x16, T, w.feat, w))) return rc;
-    return sv_forward_run(h, st, w.feat, T, sv_emb, w);
+    return sv_forward_run(h, st, w.feat, sv_batch(h->cfg, &T, 1), sv_emb, w);
+}
+
+size_t gsv_sv_batch_workspace(gsv_sv* h, const int* n_samples, int n_clips, int sample_rate) {
+    SvBatchIn in;
+    if (!h || sv_batch_in(n_samples, n_clips, sample_rate, in) != GSV_OK) return 0;
+    return sizeof(float) * sv_carve_batch(h->cfg, in.n_max, sample_rate, sv_batch(h->cfg, in.T, n_clips), nullptr).total;
+}
+
+int gsv_sv_forward_batch(gsv_sv* h, const float* feat, const int* n_frames, int n_clips, float* sv_emb, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!h || !feat || !n_frames || !sv_emb) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS) return abi_fail(GSV_ERR_ARG, "sv: %d clips (1..%d per call)", n_clips, GSV_AUX_MAX_CLIPS);
+    // the workspace of the clips' equivalent 16 kHz lengths, as gsv_sv_forward sizes it
+    int n16[GSV_AUX_MAX_CLIPS];
+    for (int i = 0; i < n_clips; ++i) {
+        if (n_frames[i] < 1 || n_frames[i] > (0x7fffffff - FB_WIN) / FB_HOP)
+            return abi_fail(GSV_ERR_ARG, "sv: clip %d: %d frames", i, n_frames[i]);
+        n16[i] = FB_WIN + FB_HOP * (n_frames[i] - 1);
+    }
+    SvBatchIn in;
+    int rc;
+    if ((rc = sv_check_batch(h, n16, n_clips, 16000, workspace, workspace_bytes, in))) return rc;
+    const SvBatch B = sv_batch(h->cfg, n_frames, n_clips);
+    const SvWs w = sv_carve_batch(h->cfg, in.n_max, 16000, B, static_cast<float*>(workspace));
+    return sv_forward_run(h, S(stream), feat, B, sv_emb, w);
+}
+
+int gsv_sv_embed_batch(gsv_sv* h, const float* wav, const int* n_samples, int n_clips, int sample_rate, float* sv_emb,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !wav || !n_samples || !sv_emb) return abi_fail(GSV_ERR_ARG, "null argument");
+    SvBatchIn in;
+    int rc;
+    if ((rc = sv_check_batch(h, n_samples, n_clips, sample_rate, workspace, workspace_bytes, in))) return rc;
+    hipStream_t st = S(stream);
+    const SvBatch B = sv_batch(h->cfg, in.T, n_clips);
+    const SvWs w = sv_carve_batch(h->cfg, in.n_max, sample_rate, B, static_cast<float*>(workspace));
+    // resample and fbank per clip (their buffers sized for the longest clip), each into its rows of the packed feat
+    long long a0 = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        const float* x16 = wav + a0;
+        if (sample_rate != 16000) {
+            if ((rc = sv_resample_run(st, wav + a0, n_samples[i], sample_rate, 16000, w.y16, w.tab))) return rc;
+            x16 = w.y16;
+        }
+        if ((rc = sv_fbank_run(h, st, x16, in.T[i], w.feat + (long long)B.feat0[i] * FB_MELS, w))) return rc;
+        a0 += n_samples[i];
+    }
+    return sv_forward_run(h, st, w.feat, B, sv_emb, w);
 }
 
 }  // extern "C"

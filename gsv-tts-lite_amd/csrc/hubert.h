@@ -8,10 +8,20 @@
 //   12 post-LN layers x = LN(x + out_proj(attn(x))), x = LN(x + fc2(gelu(fc1(x))))
 // The GEMMs are refaudio.h's fgemm_kernel; the kernels below are the pieces it does not cover.  None uses atomics:
 // every reduction has a fixed order, so a call is bit-reproducible.
+// Batches (gsv_hubert_forward_batch) pack the clips' frames as rows: fgemm has no K split and LayerNorm is per row, so
+// packing keeps every sum as it is.  The positional conv and the attention take HubClips and never mix clips; the
+// *_batch kernels share their tile bodies with the single-clip kernels, so a clip's output is bit-identical either way.
 #pragma once
 #include "refaudio.h"
 
 namespace gsv {
+
+// packed clips of one batch, by value in the kernel arguments: clip z holds rows [row0, row0 + T) of the packed
+// activations and rows [prow0, prow0 + T + k - 1) of the group-major padded copy of the positional conv
+struct HubClips {
+    int n;
+    int row0[AUX_MAX_CLIPS], prow0[AUX_MAX_CLIPS], T[AUX_MAX_CLIPS];
+};
 
 // ---- GroupNorm(C, C) of conv 0: per-channel statistics over every frame, in two deterministic passes.
 // Pass 1: block (channel tile of 64, chunk of GN_ROWS frames) -> the chunk's mean and sum of squared deviations
@@ -121,25 +131,58 @@ static __global__ void pos_pad_group_kernel(const float* __restrict__ x, int T, 
     P[i] = (t >= 0 && t < T) ? x[(long long)t * H + g * cg + c] : 0.f;
 }
 
+// batched: blockIdx.y = clip; clip z's rows of x [rows][H] -> its own zero-haloed segment of P [G][Rp][H / G]
+static __global__ void pos_pad_group_batch_kernel(const float* __restrict__ x, int H, int G, int k, long long Rp, HubClips cl,
+                                                  float* __restrict__ P) {
+    const int z = blockIdx.y, T = cl.T[z];
+    const int cg = H / G, Tp = T + k - 1;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)G * Tp * cg) return;
+    const int c = (int)(i % cg), p = (int)((i / cg) % Tp), g = (int)(i / ((long long)cg * Tp));
+    const int t = p - k / 2;
+    P[((long long)g * Rp + cl.prow0[z] + p) * cg + c] = (t >= 0 && t < T) ? x[(long long)(cl.row0[z] + t) * H + g * cg + c] : 0.f;
+}
+
 // ---- the positional conv as ONE launch over (row tile, group x K slice): block z = g * POS_SPLIT + s contracts the s-th
 // slice of group g's k * (H/G) values (an fgemm tile over the padded group-major rows) into part[s][T][H]; pos_reduce
 // then sums the slices in index order (deterministic) and applies bias, GELU and the residual.  Per-group launches left
 // 3-9 blocks per launch walking K = 6144 alone.
 constexpr int POS_SPLIT = 8;
-static __global__ __launch_bounds__(256) void pos_conv_split_kernel(const float* __restrict__ P, const float* __restrict__ w,
-                                                                    float* __restrict__ part, int T, int H, int G, int k) {
+// the tile (m0, n0) of block z over one clip: P its first padded row (group stride gstride floats), part its first
+// output row (slice stride pstride floats), T its frames
+__device__ __forceinline__ void pos_conv_tile(const float* __restrict__ P, long long gstride, const float* __restrict__ w,
+                                              float* __restrict__ part, long long pstride, int T, int H, int G, int k, int z,
+                                              int m0, int n0) {
     __shared__ float xs[64 * FG_LD];
     __shared__ float ws[64 * FG_LD];
-    const int cg = H / G, Tp = T + k - 1, Kt = k * cg;
-    const int g = blockIdx.z / POS_SPLIT, sp = blockIdx.z % POS_SPLIT;
+    const int cg = H / G, Kt = k * cg;
+    const int g = z / POS_SPLIT, sp = z % POS_SPLIT;
     const int k0 = (int)((long long)Kt * sp / POS_SPLIT), k1 = (int)((long long)Kt * (sp + 1) / POS_SPLIT);
     FGemmArgs a;
-    a.X = P + (long long)g * Tp * cg + k0; a.ldx = cg;
+    a.X = P + g * gstride + k0; a.ldx = cg;
     a.W = w + (long long)g * cg * Kt + k0; a.ldw = Kt;
-    a.Y = part + (long long)sp * T * H + g * cg; a.ldy = H;
+    a.Y = part + sp * pstride + g * cg; a.ldy = H;
     a.bias_n = nullptr; a.bias_m = nullptr; a.R = nullptr; a.ldr = 0;
     a.M = T; a.N = cg; a.K = k1 - k0; a.alpha = 1.f; a.act = 0;
-    fgemm_tile(a, blockIdx.y * 64, blockIdx.x * 64, xs, ws);
+    fgemm_tile(a, m0, n0, xs, ws);
+}
+
+static __global__ __launch_bounds__(256) void pos_conv_split_kernel(const float* __restrict__ P, const float* __restrict__ w,
+                                                                    float* __restrict__ part, int T, int H, int G, int k) {
+    const int cg = H / G, Tp = T + k - 1;
+    pos_conv_tile(P, (long long)Tp * cg, w, part, (long long)T * H, T, H, G, k, blockIdx.z, blockIdx.y * 64, blockIdx.x * 64);
+}
+
+// batched: blockIdx.x = clip * column tiles + column tile (the clip is not in z, which G * POS_SPLIT already fills);
+// row tiles past the clip's frames exit; P [G][Rp][H / G], part [POS_SPLIT][rows][H]
+static __global__ __launch_bounds__(256) void pos_conv_split_batch_kernel(const float* __restrict__ P, long long Rp,
+                                                                          const float* __restrict__ w, float* __restrict__ part,
+                                                                          int rows, int H, int G, int k, HubClips cl) {
+    const int cg = H / G, ntn = (cg + 63) / 64, z = blockIdx.x / ntn;
+    const int T = cl.T[z];
+    if ((int)blockIdx.y * 64 >= T) return;
+    pos_conv_tile(P + (long long)cl.prow0[z] * cg, Rp * cg, w, part + (long long)cl.row0[z] * H, (long long)rows * H, T, H, G,
+                  k, blockIdx.z, blockIdx.y * 64, (blockIdx.x % ntn) * 64);
 }
 
 // out[t][c] = hid[t][c] + gelu(bias[c] + sum_s part[s][t][c]), s in index order
@@ -180,15 +223,16 @@ static __global__ void wn_fold_kc_kernel(const float* __restrict__ v, const floa
 // ---- fused self-attention, head dim 64, no mask: out[t][h*64 + d] = softmax_s(scale * q_t . k_s) v_s[d].
 // Block = 32 queries of one head (128 threads); a query is 4 adjacent lanes with 16 dims each.  K / V tiles of 64 keys
 // are staged in LDS; the 64 scores of a tile stay in registers and fold into a running max / sum (online softmax), so
-// no [heads][T][T] tensor exists.  All 32 queries read the same key row: every ds_read_b128 is 4 distinct 16-B slots
-// (banks 0-3, 16-19, 32-35, 48-51) broadcast to 16 lanes each, conflict-free.
+// no [heads][T][T] tensor exists and T has no limit.  All 32 queries read the same key row: every ds_read_b128 is 4
+// distinct 16-B slots (banks 0-3, 16-19, 32-35, 48-51) broadcast to 16 lanes each, conflict-free.
 // qkv [T][ld]: q at column h*64, k at H + h*64, v at 2H + h*64.
 constexpr int ATT_QB = 32, ATT_KT = 64;
-static __global__ __launch_bounds__(128) void hubert_attn_kernel(const float* __restrict__ qkv, long long ld, int T, int H,
-                                                                 float scale, float* __restrict__ out, long long ldo) {
+// query block qb of head h over the T rows at qkv (the keys are those T rows)
+__device__ __forceinline__ void hubert_attn_block(const float* __restrict__ qkv, long long ld, int T, int H, float scale,
+                                                  float* __restrict__ out, long long ldo, int qb, int h) {
     __shared__ float4 ks[ATT_KT * 16], vs[ATT_KT * 16];
     const int tid = threadIdx.x, part = tid & 3;
-    const int h = blockIdx.y, row = blockIdx.x * ATT_QB + (tid >> 2);
+    const int row = qb * ATT_QB + (tid >> 2);
     float q[16], o[16];
     {
         const float* qp = qkv + (long long)row * ld + h * 64 + part * 16;
@@ -253,6 +297,21 @@ static __global__ __launch_bounds__(128) void hubert_attn_kernel(const float* __
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         reinterpret_cast<float4*>(op)[i] = make_float4(o[4 * i] * inv, o[4 * i + 1] * inv, o[4 * i + 2] * inv, o[4 * i + 3] * inv);
+}
+
+static __global__ __launch_bounds__(128) void hubert_attn_kernel(const float* __restrict__ qkv, long long ld, int T, int H,
+                                                                 float scale, float* __restrict__ out, long long ldo) {
+    hubert_attn_block(qkv, ld, T, H, scale, out, ldo, blockIdx.x, blockIdx.y);
+}
+
+// batched: blockIdx.z = clip, whose queries attend to its own rows only; query blocks past the clip's frames exit
+static __global__ __launch_bounds__(128) void hubert_attn_batch_kernel(const float* __restrict__ qkv, long long ld, int H,
+                                                                       float scale, float* __restrict__ out, long long ldo,
+                                                                       HubClips cl) {
+    const int z = blockIdx.z, T = cl.T[z];
+    if ((int)blockIdx.x * ATT_QB >= T) return;
+    const long long r0 = cl.row0[z];
+    hubert_attn_block(qkv + r0 * ld, ld, T, H, scale, out + r0 * ldo, ldo, blockIdx.x, blockIdx.y);
 }
 
 }  // namespace gsv

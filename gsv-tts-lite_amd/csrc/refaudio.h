@@ -21,6 +21,10 @@ namespace gsv {
 
 typedef float fa16 __attribute__((ext_vector_type(16)));
 
+// clips of one batched CN-HuBERT / ERes2NetV2 call (GSV_AUX_MAX_CLIPS): the per-clip geometry travels by value in the
+// kernel arguments
+constexpr int AUX_MAX_CLIPS = 64;
+
 struct FGemmArgs {
     const float* X; long long ldx;    // [M] rows of K values, stride ldx (may be < K)
     const float* W; long long ldw;    // [N] rows of K values

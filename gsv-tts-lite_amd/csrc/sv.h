@@ -14,6 +14,9 @@
 // folded into the weights and a bias at finalize.  A second input source serves Res2Net's sp + spx[i] (summed in the
 // prologue) and AFF's cat(x, y) (a second K range); the output goes through a channel slice, so torch.cat is no copy.
 // Nothing uses atomics or scratch: every sum has a fixed order, so a call is bit-reproducible.
+// Batches (gsv_sv_forward_batch / gsv_sv_embed_batch) run each conv once for all clips: every clip keeps its own padded
+// images, sv_conv_batch_kernel takes the clip as grid z and shares sv_conv_kernel's tile, so a clip's embedding is
+// bit-identical to its single-clip call.
 #pragma once
 #include "refaudio.h"
 
@@ -172,7 +175,7 @@ __device__ __forceinline__ float sv_act(float v, int act) {
 // else each (source, tap) of Cin values.  Staging: 8 rows x 32 k per pass.
 constexpr int SV_KC = 32, SV_LD = SV_KC + 1;
 template <int WM, int WN>
-__global__ __launch_bounds__(256) void sv_conv_kernel(SvConvArgs a) {
+__device__ __forceinline__ void sv_conv_tile(const SvConvArgs& a) {
     constexpr int BM = 32 * WM, BN = 32 * WN, PM = BM / 8, PN = BN / 8;
     __shared__ float xs[BM * SV_LD];
     __shared__ float ws[BN * SV_LD];
@@ -260,6 +263,37 @@ __global__ __launch_bounds__(256) void sv_conv_kernel(SvConvArgs a) {
             a.Y[o * a.ldy + n] = v;
         }
     }
+}
+
+template <int WM, int WN>
+__global__ __launch_bounds__(256) void sv_conv_kernel(SvConvArgs a) {
+    sv_conv_tile<WM, WN>(a);
+}
+
+// a batch of clips, each with its own padded images in every buffer (never concatenated along T: a stride-2 conv would
+// read across the separators): clip z's input image starts in_off[z] pixels into X1 / X2, its output image out_off[z]
+// pixels into Y / R / A / B; Ti / To its frames.  F is the same for every clip.
+struct SvClips {
+    long long in_off[AUX_MAX_CLIPS], out_off[AUX_MAX_CLIPS];
+    int Ti[AUX_MAX_CLIPS], To[AUX_MAX_CLIPS];
+};
+
+// blockIdx.z = clip; row tiles past the clip's Fo * To pixels exit.  The tile is sv_conv_kernel's, so every clip's
+// output is bit-identical to its single-clip call.
+template <int WM, int WN>
+__global__ __launch_bounds__(256) void sv_conv_batch_kernel(SvConvArgs a, SvClips cl) {
+    const int z = blockIdx.z;
+    a.To = cl.To[z];
+    a.Tpi = cl.Ti[z] + 2;
+    if ((int)blockIdx.y * 32 * WM >= a.Fo * a.To) return;
+    const long long io = cl.in_off[z], oo = cl.out_off[z];
+    a.X1 += io * a.ldx;
+    if (a.X2) a.X2 += io * a.ldx;
+    a.Y += oo * a.ldy;
+    if (a.R) a.R += oo * a.ldr;
+    if (a.A) a.A += oo * a.lda;
+    if (a.B) a.B += oo * a.ldb;
+    sv_conv_tile<WM, WN>(a);
 }
 
 // emb[c * F + f] = (sum_t X[f][t][c]) / T over the padded [F + 2][T + 2][C] interior, t in order (forward3's

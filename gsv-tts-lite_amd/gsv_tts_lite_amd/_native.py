@@ -26,10 +26,10 @@ EXPORTS = [
     "gsv_ref_create", "gsv_ref_destroy", "gsv_ref_load_tensor", "gsv_ref_finalize", "gsv_ref_workspace",
     "gsv_ref_spectrogram", "gsv_ref_get_ge", "gsv_ref_extract_latent",
     "gsv_hubert_create", "gsv_hubert_destroy", "gsv_hubert_load_tensor", "gsv_hubert_finalize", "gsv_hubert_frames",
-    "gsv_hubert_workspace", "gsv_hubert_forward",
+    "gsv_hubert_workspace", "gsv_hubert_forward", "gsv_hubert_batch_workspace", "gsv_hubert_forward_batch",
     "gsv_sv_create", "gsv_sv_destroy", "gsv_sv_load_tensor", "gsv_sv_finalize", "gsv_sv_resample_length",
     "gsv_sv_resample_workspace", "gsv_sv_resample", "gsv_sv_frames", "gsv_sv_workspace", "gsv_sv_fbank", "gsv_sv_forward",
-    "gsv_sv_embed",
+    "gsv_sv_embed", "gsv_sv_batch_workspace", "gsv_sv_forward_batch", "gsv_sv_embed_batch",
     "gsv_roberta_create", "gsv_roberta_destroy", "gsv_roberta_load_tensor", "gsv_roberta_finalize", "gsv_roberta_workspace",
     "gsv_roberta_forward", "gsv_roberta_features",
 ]
@@ -60,6 +60,7 @@ class RefConfig(ctypes.Structure):
 
 
 HUBERT_MAX_CONV = 8
+AUX_MAX_CLIPS = 64      # GSV_AUX_MAX_CLIPS: clips per gsv_hubert_forward_batch / gsv_sv_*_batch call
 
 
 class HubertConfig(ctypes.Structure):
@@ -91,6 +92,7 @@ def lib():
             "g.build()\"` (hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback for the hot path." % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     vp, i, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
+    ip = ctypes.POINTER(ctypes.c_int)   # host int arrays
     L.gsv_version.restype = i
     L.gsv_last_error.restype = ctypes.c_char_p
     sig = {
@@ -142,6 +144,7 @@ def lib():
         "gsv_hubert_finalize": [vp, vp],
         "gsv_hubert_frames": [vp, i],
         "gsv_hubert_forward": [vp, vp, i, vp, vp, sz, vp],
+        "gsv_hubert_forward_batch": [vp, vp, ip, i, vp, vp, sz, vp],
         "gsv_sv_create": [ctypes.POINTER(SvConfig), ctypes.POINTER(vp)],
         "gsv_sv_destroy": [vp],
         "gsv_sv_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
@@ -152,6 +155,8 @@ def lib():
         "gsv_sv_fbank": [vp, vp, i, vp, vp, sz, vp],
         "gsv_sv_forward": [vp, vp, i, vp, vp, sz, vp],
         "gsv_sv_embed": [vp, vp, i, i, vp, vp, sz, vp],
+        "gsv_sv_forward_batch": [vp, vp, ip, i, vp, vp, sz, vp],
+        "gsv_sv_embed_batch": [vp, vp, ip, i, i, vp, vp, sz, vp],
         "gsv_roberta_create": [ctypes.POINTER(RobertaConfig), ctypes.POINTER(vp)],
         "gsv_roberta_destroy": [vp],
         "gsv_roberta_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
@@ -181,6 +186,10 @@ def lib():
     L.gsv_sv_resample_workspace.restype = sz
     L.gsv_sv_workspace.argtypes = [vp, i, i]
     L.gsv_sv_workspace.restype = sz
+    L.gsv_hubert_batch_workspace.argtypes = [vp, ip, i]
+    L.gsv_hubert_batch_workspace.restype = sz
+    L.gsv_sv_batch_workspace.argtypes = [vp, ip, i, i]
+    L.gsv_sv_batch_workspace.restype = sz
     L.gsv_roberta_workspace.argtypes = [vp, i, i, i]
     L.gsv_roberta_workspace.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]

@@ -139,6 +139,51 @@ class CNHubertNative:
         a = torch.as_tensor(wav16k).to(device=self.device, dtype=torch.float32).reshape(-1)
         return self(torch.cat([a, a.new_zeros(PROMPT_PAD)]))
 
+    def _grow_ws(self, need: int):
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def batch(self, wavs):
+        """a list of waveforms as __call__ takes them -> [ssl [1, hidden, Th_i]]: the clips run packed
+        (gsv_hubert_forward_batch, AUX_MAX_CLIPS per call), each result bit-identical to self(wav) whatever else is in the
+        list.  ValueError naming the index of a clip that is not one mono waveform or is too short."""
+        clips = []
+        for i, w in enumerate(wavs):
+            a = torch.as_tensor(w)
+            if a.dim() == 2 and a.shape[0] == 1:
+                a = a[0]
+            if a.dim() != 1:
+                raise ValueError("CN-HuBERT: clip %d is not one mono 16 kHz waveform ([n] or [1, n]); got shape %s"
+                                 % (i, tuple(a.shape)))
+            if self.frames(a.numel()) < 1:
+                raise ValueError("CN-HuBERT: clip %d: %d samples are too short for the feature encoder" % (i, a.numel()))
+            clips.append(a.to(device=self.device, dtype=torch.float32).contiguous())
+        L, out = N.lib(), []
+        for c0 in range(0, len(clips), N.AUX_MAX_CLIPS):
+            chunk = clips[c0:c0 + N.AUX_MAX_CLIPS]
+            ns = (ctypes.c_int * len(chunk))(*[a.numel() for a in chunk])
+            Th = [self.frames(a.numel()) for a in chunk]
+            ws = self._grow_ws(L.gsv_hubert_batch_workspace(self._h, ns, len(chunk)))
+            audio = torch.cat(chunk)
+            ssl = torch.empty(self.hidden * sum(Th), dtype=torch.float32, device=self.device)
+            N.check(L.gsv_hubert_forward_batch(self._h, audio.data_ptr(), ns, len(chunk), ssl.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), N.current_stream_ptr(self.device)))
+            off = 0
+            for t in Th:
+                out.append(ssl[self.hidden * off:self.hidden * (off + t)].view(1, self.hidden, t))
+                off += t
+        return out
+
+    def prompt_ssl_batch(self, wavs):
+        """prompt_ssl of every waveform in the list, run as one batch: [ssl [1, hidden, Th_i]]"""
+        padded = []
+        for w in wavs:
+            a = torch.as_tensor(w).to(device=self.device, dtype=torch.float32).reshape(-1)
+            padded.append(torch.cat([a, a.new_zeros(PROMPT_PAD)]))
+        return self.batch(padded)
+
 
 def load_cnhubert(path, device) -> CNHubertNative:
     """a Hugging Face chinese-hubert-base directory (loader.read_cnhubert) on the device"""

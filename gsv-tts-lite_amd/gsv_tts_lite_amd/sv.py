@@ -134,7 +134,9 @@ class SVNative:
         return N.lib().gsv_sv_frames(self._h, int(n_samples), int(sample_rate))
 
     def _workspace(self, n_samples, sample_rate):
-        need = N.lib().gsv_sv_workspace(self._h, int(n_samples), int(sample_rate))
+        return self._grow_ws(N.lib().gsv_sv_workspace(self._h, int(n_samples), int(sample_rate)))
+
+    def _grow_ws(self, need: int):
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -185,6 +187,52 @@ class SVNative:
         emb = torch.empty(1, self.emb_dim, dtype=torch.float32, device=self.device)
         N.check(N.lib().gsv_sv_embed(self._h, a.data_ptr(), n, int(sample_rate), emb.data_ptr(), ws.data_ptr(), ws.numel(),
                                      N.current_stream_ptr(self.device)))
+        return emb
+
+    # Batches: every conv runs once for all clips of a chunk of AUX_MAX_CLIPS (gsv_sv_*_batch); row i is bit-identical
+    # to the single-clip call on clip i whatever else is in the list.
+    def forward3_batch(self, feats):
+        """forward3 of every feature matrix in the list ([T_i, 80] or [1, T_i, 80]) -> [n, emb_dim]"""
+        fs = []
+        for i, f in enumerate(feats):
+            f = torch.as_tensor(f)
+            if f.dim() == 3 and f.shape[0] == 1:
+                f = f[0]
+            if f.dim() != 2 or f.shape[1] != FEAT_DIM or f.shape[0] < 1:
+                raise ValueError("forward3_batch: clip %d is not fbank features [T, 80] or [1, T, 80], T >= 1; got %s"
+                                 % (i, tuple(f.shape)))
+            fs.append(f.to(device=self.device, dtype=torch.float32).contiguous())
+        L = N.lib()
+        emb = torch.empty(len(fs), self.emb_dim, dtype=torch.float32, device=self.device)
+        for c0 in range(0, len(fs), N.AUX_MAX_CLIPS):
+            chunk = fs[c0:c0 + N.AUX_MAX_CLIPS]
+            T = (ctypes.c_int * len(chunk))(*[f.shape[0] for f in chunk])
+            n16 = (ctypes.c_int * len(chunk))(*[400 + 160 * (f.shape[0] - 1) for f in chunk])
+            ws = self._grow_ws(L.gsv_sv_batch_workspace(self._h, n16, len(chunk), SAMPLE_RATE))
+            feat = torch.cat(chunk)
+            N.check(L.gsv_sv_forward_batch(self._h, feat.data_ptr(), T, len(chunk), emb[c0].data_ptr(), ws.data_ptr(),
+                                           ws.numel(), N.current_stream_ptr(self.device)))
+        return emb
+
+    def embed_batch(self, wavs, sample_rate: int):
+        """embed of every waveform in the list ([n_i] or [1, n_i], all at sample_rate) -> sv_emb [n, emb_dim]; ValueError
+        naming the index of a clip that is not mono or is shorter than one fbank frame"""
+        clips = []
+        for i, w in enumerate(wavs):
+            a = _mono(w, "ERes2NetV2 (clip %d)" % i).to(device=self.device, dtype=torch.float32).contiguous()
+            if self.frames(a.numel(), sample_rate) < 1:
+                raise ValueError("ERes2NetV2: clip %d: %d samples at %d Hz are too short for one fbank frame (400 samples "
+                                 "at 16 kHz)" % (i, a.numel(), sample_rate))
+            clips.append(a)
+        L = N.lib()
+        emb = torch.empty(len(clips), self.emb_dim, dtype=torch.float32, device=self.device)
+        for c0 in range(0, len(clips), N.AUX_MAX_CLIPS):
+            chunk = clips[c0:c0 + N.AUX_MAX_CLIPS]
+            ns = (ctypes.c_int * len(chunk))(*[a.numel() for a in chunk])
+            ws = self._grow_ws(L.gsv_sv_batch_workspace(self._h, ns, len(chunk), int(sample_rate)))
+            wav = torch.cat(chunk)
+            N.check(L.gsv_sv_embed_batch(self._h, wav.data_ptr(), ns, len(chunk), int(sample_rate), emb[c0].data_ptr(),
+                                         ws.data_ptr(), ws.numel(), N.current_stream_ptr(self.device)))
         return emb
 
 

@@ -35,6 +35,7 @@ gsv_align_viterbi, replacing TTS.py:1744-1797) and the word-timing / text-span b
 from __future__ import annotations
 
 import logging
+import numbers
 import os
 import re
 import threading
@@ -246,7 +247,14 @@ class TTS:
         get_ge run on the device.  v2Pro / v2ProPlus add the ERes2Net embedding sv_emb [1, 20480]: the one passed, else the
         one this path's cache entry holds, else ERes2NetV2 on the device (16 kHz resample + fbank + forward3) from
         models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, kept loaded only when always_load_sv is set.  Without that
-        checkpoint ge has no sv term (a warning says so).  The entry keeps the sv_emb, so another SoVITS model reuses it."""
+        checkpoint ge has no sv term (a warning says so).  The entry keeps the sv_emb, so another SoVITS model reuses it.
+
+        A list of keys caches many speakers in one call (what the reference's cache_spk_audio(*paths) does): `audio` a list
+        with one waveform per key, `ge` / `sv_emb` None or lists of the same length (None entries allowed).  ERes2NetV2 is
+        loaded once and runs every clip that needs an sv_emb in one batched pass; each entry equals what a single-key call
+        gives.  Any other key (a str, a tuple) is one key, as before."""
+        if isinstance(spk_audio_paths, list):
+            return self._cache_spk_batch(spk_audio_paths, sovits_model, ge, audio, sv_emb)
         sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
         entry = self.spk_audio_cache.get(spk_audio_paths)
         if ge is None:
@@ -276,6 +284,63 @@ class TTS:
             entry["sv_emb"] = torch.as_tensor(sv_emb).to(self.tts_config.device).float().reshape(1, -1)
 
     @staticmethod
+    def _per_key(v, n, name, one):
+        """v for each of n keys: [v] * n when one(v) holds, else v as a list of n entries (ValueError otherwise)"""
+        if one(v):
+            return [v] * n
+        if not isinstance(v, (list, tuple)):
+            raise ValueError("%s must be a list with one entry per key (%d keys); got %s" % (name, n, type(v).__name__))
+        if len(v) != n:
+            raise ValueError("%s has %d entries for %d keys" % (name, len(v), n))
+        return list(v)
+
+    def _cache_spk_batch(self, keys, sovits_model, ge, audio, sv_emb):
+        n = len(keys)
+        ges = self._per_key(ge, n, "ge", lambda v: v is None)
+        svs = self._per_key(sv_emb, n, "sv_emb", lambda v: v is None)
+        auds = self._per_key(audio, n, "audio", lambda v: v is None)
+        for i in range(n):
+            if ges[i] is None and auds[i] is None:
+                raise NotImplementedError("decoding / resampling audio files is outside this build's scope; key %d (%r) "
+                                          "needs ge=[1, gin, 1] or audio=<waveform>" % (i, keys[i]))
+        sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
+        todo = [i for i in range(n) if ges[i] is None]
+        if todo:
+            if sovits_model not in self.sovits_models:
+                self.load_sovits_model(sovits_model)
+            sovits = self.sovits_models[sovits_model]
+            vq = sovits.vq_model
+            wav = {}
+            for i in todo:
+                a = torch.as_tensor(auds[i]).to(self.tts_config.device).float().reshape(1, -1)
+                peak = a.abs().max()
+                if peak > 1:                       # TTS.py:1586-1588
+                    a = a / min(2, float(peak))
+                wav[i] = a
+            if getattr(vq, "is_v2pro", False):
+                need = []
+                for i in todo:
+                    entry = self.spk_audio_cache.get(keys[i])
+                    if svs[i] is None and entry is not None and entry.get("sv_emb") is not None:
+                        svs[i] = entry["sv_emb"]
+                    elif svs[i] is None:
+                        need.append(i)
+                if need and os.path.isfile(self.sv_path):
+                    e = self._sv_embed_batch([wav[i] for i in need], self._model_rate(sovits))
+                    for j, i in enumerate(need):
+                        svs[i] = e[j:j + 1]
+                elif need:
+                    log.warning("ERes2NetV2 checkpoint %s not found: ge of %s has no speaker-verification term; pass "
+                                "sv_emb=[1, 20480] or install the checkpoint", self.sv_path, [keys[i] for i in need])
+            for i in todo:
+                ges[i] = vq.get_ge(vq.spectrogram(wav[i]), svs[i])
+        for i, k in enumerate(keys):
+            entry = self.spk_audio_cache.setdefault(k, {"ge": {}})
+            entry["ge"][sovits_model] = ges[i].to(self.tts_config.device)
+            if svs[i] is not None:
+                entry["sv_emb"] = torch.as_tensor(svs[i]).to(self.tts_config.device).float().reshape(1, -1)
+
+    @staticmethod
     def _model_rate(sovits) -> int:
         try:
             return int(sovits.hps.data.sampling_rate)
@@ -289,6 +354,17 @@ class TTS:
             if self.sv_model is None:
                 self.sv_model = load_sv(self.sv_path, self.tts_config.device)
             return self.sv_model.embed(audio, sample_rate)
+        finally:
+            if not self.always_load_sv:
+                self.sv_model = None
+
+    def _sv_embed_batch(self, wavs, sample_rate):
+        """_sv_embed of every waveform in the list, one batched pass -> [n, 20480]"""
+        from .sv import load_sv
+        try:
+            if self.sv_model is None:
+                self.sv_model = load_sv(self.sv_path, self.tts_config.device)
+            return self.sv_model.embed_batch(wavs, sample_rate)
         finally:
             if not self.always_load_sv:
                 self.sv_model = None
@@ -322,7 +398,16 @@ class TTS:
         transposed as in TTS._get_prompt), or `audio`, the prompt waveform as mono fp32 at 16 kHz ([n] or [1, n]): then
         CN-HuBERT (TTS._get_prompt: + 0.3 s of zeros) and extract_latent run on the device.  CN-HuBERT is loaded from
         models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Audio at another
-        `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample)."""
+        `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample).
+
+        A list of keys caches many prompts in one call (the reference's list form): `audio` a list with one waveform per
+        key, `prompt_audio_texts` one str for all or a list, `phones1` one list[int] for all or a list of them, `bert1`
+        None or a list, `sample_rate` one int or a list.  CN-HuBERT is loaded once and runs every clip in one batched pass,
+        then extract_latent runs per clip; each entry equals what a single-key call gives.  Lengths and empty texts are
+        checked before any device work.  Any other key (a str, a tuple) is one key, as before."""
+        if isinstance(prompt_audio_paths, list):
+            return self._cache_prompt_batch(prompt_audio_paths, prompt_audio_texts, prompt, phones1, bert1, ssl_content,
+                                            sovits_model, audio, sample_rate)
         if not prompt_audio_texts:
             raise ValueError("prompt_audio_text must not be empty")
         if prompt is None and ssl_content is None and audio is not None:
@@ -358,6 +443,60 @@ class TTS:
                 raise ValueError("audio must be one mono waveform at 16 kHz ([n] or [1, n]); resampling and channel mixing "
                                  "are outside this build's scope; got shape %s" % (tuple(a.shape),))
             return self.cnhubert_model.prompt_ssl(a)
+        finally:
+            if not self.always_load_cnhubert:
+                self.cnhubert_model = None
+
+    def _cache_prompt_batch(self, keys, texts, prompt, phones1, bert1, ssl_content, sovits_model, audio, sample_rate):
+        n = len(keys)
+        if prompt is not None or ssl_content is not None:
+            raise ValueError("a list of keys takes audio=[one waveform per key]; prompt= / ssl_content= are single-key forms")
+        texts = self._per_key(texts, n, "prompt_audio_texts", lambda v: isinstance(v, str))
+        for i, t in enumerate(texts):
+            if not t:
+                raise ValueError("prompt_audio_texts[%d] must not be empty" % i)
+        if audio is None:
+            raise NotImplementedError("decoding / resampling audio files and G2P are outside this build's scope; a list of "
+                                      "keys needs audio=[one mono fp32 waveform per key] and phones1")
+        auds = self._per_key(audio, n, "audio", lambda v: False)
+        if phones1 is None:
+            raise NotImplementedError("G2P is outside this build's scope; pass phones1=list[int] or one list[int] per key")
+        phones = self._per_key(phones1, n, "phones1",
+                               lambda v: isinstance(v, (list, tuple)) and (not v or isinstance(v[0], numbers.Integral)))
+        berts = self._per_key(bert1, n, "bert1", lambda v: v is None)
+        rates = self._per_key(sample_rate, n, "sample_rate", lambda v: isinstance(v, numbers.Integral))
+        wavs = []
+        for i, a in enumerate(auds):
+            a = torch.as_tensor(a)
+            if a.dim() == 2 and a.shape[0] == 1:
+                a = a[0]
+            if a.dim() != 1:
+                raise ValueError("audio[%d] must be one mono waveform ([n] or [1, n]); resampling and channel mixing are "
+                                 "outside this build's scope; got shape %s" % (i, tuple(a.shape)))
+            wavs.append(a)
+        for i, r in enumerate(rates):
+            if int(r) != 16000:
+                from .sv import resample
+                wavs[i] = resample(wavs[i], int(r), 16000, self.tts_config.device)
+        ssl = self._cnhubert_ssl_batch(wavs)
+        sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
+        if sovits_model not in self.sovits_models:
+            self.load_sovits_model(sovits_model)
+        vq = self.sovits_models[sovits_model].vq_model
+        for i, k in enumerate(keys):
+            p = vq.extract_latent(ssl[i])[0, 0].unsqueeze(0)
+            b = berts[i] if berts[i] is not None else torch.zeros(len(phones[i]), 1024)
+            self.prompt_audio_cache[k] = {
+                "prompt": p.to(self.tts_config.device), "phones1": list(phones[i]),
+                "bert1": b.to(self.tts_config.device), "text": texts[i]}
+
+    def _cnhubert_ssl_batch(self, wavs):
+        """_cnhubert_ssl of every 16 kHz waveform in the list, one batched pass (hubert.py)"""
+        from .hubert import load_cnhubert
+        try:
+            if self.cnhubert_model is None:
+                self.cnhubert_model = load_cnhubert(self.cnhubert_path, self.tts_config.device)
+            return self.cnhubert_model.prompt_ssl_batch(wavs)
         finally:
             if not self.always_load_cnhubert:
                 self.cnhubert_model = None

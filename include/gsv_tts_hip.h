@@ -404,6 +404,16 @@ size_t gsv_hubert_workspace(gsv_hubert* h, int n_samples);
  * (last_hidden_state transposed, what gsv_ref_extract_latent takes).  Nothing is allocated. */
 int gsv_hubert_forward(gsv_hubert* h, const float* audio, int n_samples, float* ssl, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* Batches of CN-HuBERT / ERes2NetV2 clips: up to GSV_AUX_MAX_CLIPS clips in one call, each clip's output bit-identical to
+ * the single-clip call on that clip whatever else is in the batch and in any order.  n_samples / n_frames are HOST arrays
+ * of n_clips; nothing is allocated or copied from the host inside the calls.  GSV_ERR_ARG (gsv_last_error names the clip)
+ * for n_clips outside 1..GSV_AUX_MAX_CLIPS, a clip too short, a bad rate, a workspace too small or not 16-byte aligned. */
+#define GSV_AUX_MAX_CLIPS 64
+/* device bytes of the workspace of gsv_hubert_forward_batch over these clips; 0 when a clip is too short */
+size_t gsv_hubert_batch_workspace(gsv_hubert* h, const int* n_samples, int n_clips);
+/* audio: the clips' 16 kHz samples back to back; ssl: clip i's [hidden][Th_i] block at offset hidden * sum_{j<i} Th_j */
+int gsv_hubert_forward_batch(gsv_hubert* h, const float* audio, const int* n_samples, int n_clips, float* ssl,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ERes2NetV2, once per new speaker: the speaker-verification embedding sv_emb that get_ge adds for v2Pro / v2ProPlus, as
  * TTS.cache_spk_audio computes it (gsv_tts/TTS.py:1346-1389, 1591-1610; GPT_SoVITS/SV/sv.py): the model-rate waveform
@@ -448,6 +458,16 @@ int gsv_sv_forward(gsv_sv* h, const float* feat, int n_frames, float* sv_emb, vo
 /* wav fp32 [n_samples] at sample_rate (mono, peak-normalised by the caller) -> resample to 16 kHz -> fbank -> sv_emb */
 int gsv_sv_embed(gsv_sv* h, const float* wav, int n_samples, int sample_rate, float* sv_emb, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* Batches (GSV_AUX_MAX_CLIPS, see gsv_hubert_forward_batch): device bytes of the workspace of gsv_sv_embed_batch over
+ * these clips at sample_rate; it also covers gsv_sv_forward_batch of clips whose equivalent 16 kHz lengths
+ * 400 + 160 * (n_frames - 1) are given at 16000.  0 on bad arguments. */
+size_t gsv_sv_batch_workspace(gsv_sv* h, const int* n_samples, int n_clips, int sample_rate);
+/* feat: the clips' [n_frames_i][80] fbank rows back to back -> sv_emb [n_clips][emb_dim] (forward3 of each clip) */
+int gsv_sv_forward_batch(gsv_sv* h, const float* feat, const int* n_frames, int n_clips, float* sv_emb,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* wav: the clips back to back at sample_rate (peak-normalised by the caller) -> sv_emb [n_clips][emb_dim] */
+int gsv_sv_embed_batch(gsv_sv* h, const float* wav, const int* n_samples, int n_clips, int sample_rate, float* sv_emb,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* Chinese RoBERTa, once per request: hidden_states[-3] of BertForMaskedLM (chinese-roberta-wwm-ext-large) and the
  * phone features CNRoberta._forward_pytorch builds from them (gsv_tts/GPT_SoVITS/Featurizer/cnroberta.py), fp32 in every
