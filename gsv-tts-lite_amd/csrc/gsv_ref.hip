@@ -1,7 +1,8 @@
 // C-ABI of the reference-audio path (include/gsv_tts_hip.h, "reference audio" section; kernels in refaudio.h), of
 // CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm) and of ERes2NetV2 with its resampler and
 // fbank (gsv_sv_*; kernels in sv.h, which uses the same fgemm for the DFT and the mel filter bank) and of Chinese RoBERTa
-// (gsv_roberta_*; kernels in roberta.h, which reuses hubert.h's LayerNorm and fgemm's tile body).
+// (gsv_roberta_*; kernels in roberta.h, which reuses hubert.h's LayerNorm and fgemm's tile body), and the WAV sample
+// conversion in front of them all (gsv_wav_*; kernel in wavpcm.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,9 +18,12 @@
 #include "refaudio.h"
 #include "roberta.h"
 #include "sv.h"
+#include "wavpcm.h"
 
 using namespace gsv;
 
+static_assert(WAV_U8 == GSV_PCM_U8 && WAV_S16 == GSV_PCM_S16 && WAV_S24 == GSV_PCM_S24 && WAV_S32 == GSV_PCM_S32 &&
+              WAV_F32 == GSV_PCM_F32 && WAV_F64 == GSV_PCM_F64, "wavpcm.h's formats are the ABI's GSV_PCM_* codes");
 static_assert(AUX_MAX_CLIPS == GSV_AUX_MAX_CLIPS, "the kernels' per-clip argument arrays hold GSV_AUX_MAX_CLIPS clips");
 
 #define RCHK(expr)                                                                                        \
@@ -1495,6 +1499,55 @@ int gsv_roberta_features(gsv_roberta* h, const int* ids, const int* seq_starts, 
     if (n_phones > 0) rb_phone_gather_kernel<<<n_phones, 256, 0, st>>>(w.hid, total_rows, h->cfg.hidden, phone_index, out);
     RCHK(hipGetLastError());
     return GSV_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// WAV data chunk -> fp32 mono (wavpcm.h)
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int gsv_wav_to_mono_batch(const void* pcm, size_t pcm_bytes, const gsv_wav_clip* clips, int n_clips, float* out, void* stream) {
+    if (!pcm || !clips || !out) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS) return abi_fail(GSV_ERR_ARG, "wav: %d clips (1..%d per call)", n_clips, GSV_AUX_MAX_CLIPS);
+    WavClips cl;
+    long long out0 = 0;
+    int n_max = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        const gsv_wav_clip& c = clips[i];
+        if (c.format < 0 || c.format >= WAV_N_FORMATS) return abi_fail(GSV_ERR_ARG, "wav: clip %d: unknown sample format %d", i, c.format);
+        if (c.channels < 1 || c.channels > 2) return abi_fail(GSV_ERR_ARG, "wav: clip %d: %d channels (1 or 2)", i, c.channels);
+        if (c.n_frames < 1) return abi_fail(GSV_ERR_ARG, "wav: clip %d: %d frames", i, c.n_frames);
+        const long long frame = (long long)wav_sample_bytes(c.format) * c.channels;
+        if (c.byte_offset < 0 || (unsigned long long)c.byte_offset > pcm_bytes ||
+            (unsigned long long)c.n_frames * frame > pcm_bytes - (unsigned long long)c.byte_offset)
+            return abi_fail(GSV_ERR_ARG, "wav: clip %d: %d frames at byte %lld run past the %zu bytes of pcm", i, c.n_frames,
+                            (long long)c.byte_offset, pcm_bytes);
+        cl.off[i] = c.byte_offset;
+        cl.out0[i] = out0;
+        cl.n[i] = c.n_frames;
+        cl.fmt[i] = c.format;
+        cl.ch[i] = c.channels;
+        out0 += c.n_frames;
+        n_max = std::max(n_max, (int)c.n_frames);
+    }
+    wav_to_mono_kernel<<<dim3((unsigned)((n_max + 255) / 256), n_clips), 256, 0, S(stream)>>>(
+        static_cast<const unsigned char*>(pcm), cl, out);
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int gsv_wav_to_mono(const void* pcm, size_t pcm_bytes, int n_frames, int format, int channels, float* out, void* stream) {
+    if (format < 0 || format >= WAV_N_FORMATS || channels < 1 || channels > 2)
+        return abi_fail(GSV_ERR_ARG, "wav: format %d with %d channels (formats 0..%d, 1 or 2 channels)", format, channels,
+                        WAV_N_FORMATS - 1);
+    gsv_wav_clip c;
+    c.byte_offset = 0;
+    c.n_frames = n_frames;
+    c.format = (int16_t)format;
+    c.channels = (int16_t)channels;
+    return gsv_wav_to_mono_batch(pcm, pcm_bytes, &c, 1, out, stream);
 }
 
 }  // extern "C"

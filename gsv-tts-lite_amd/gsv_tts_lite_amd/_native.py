@@ -32,6 +32,7 @@ EXPORTS = [
     "gsv_sv_embed", "gsv_sv_batch_workspace", "gsv_sv_forward_batch", "gsv_sv_embed_batch",
     "gsv_roberta_create", "gsv_roberta_destroy", "gsv_roberta_load_tensor", "gsv_roberta_finalize", "gsv_roberta_workspace",
     "gsv_roberta_forward", "gsv_roberta_features",
+    "gsv_wav_to_mono", "gsv_wav_to_mono_batch",
 ]
 
 
@@ -72,6 +73,15 @@ class HubertConfig(ctypes.Structure):
 class SvConfig(ctypes.Structure):
     _fields_ = [("m_channels", ctypes.c_int), ("blocks", ctypes.c_int * 4), ("width", ctypes.c_int * 4),
                 ("scale", ctypes.c_int), ("expansion", ctypes.c_int), ("feat_dim", ctypes.c_int)]
+
+
+class WavClip(ctypes.Structure):
+    """gsv_wav_clip: one clip of gsv_wav_to_mono_batch"""
+    _fields_ = [("byte_offset", ctypes.c_int64), ("n_frames", ctypes.c_int32), ("format", ctypes.c_int16),
+                ("channels", ctypes.c_int16)]
+
+
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # GSV_PCM_*
 
 
 class RobertaConfig(ctypes.Structure):
@@ -163,6 +173,8 @@ def lib():
         "gsv_roberta_finalize": [vp, vp],
         "gsv_roberta_forward": [vp, vp, vp, i, i, i, vp, vp, sz, vp],
         "gsv_roberta_features": [vp, vp, vp, i, i, i, vp, i, vp, vp, sz, vp],
+        "gsv_wav_to_mono": [vp, sz, i, i, i, vp, vp],
+        "gsv_wav_to_mono_batch": [vp, sz, ctypes.POINTER(WavClip), i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

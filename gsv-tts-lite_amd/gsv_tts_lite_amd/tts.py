@@ -17,12 +17,18 @@ loads it in __init__, auto_bert=True (the default) loads it on the first infer /
 holds a CJK ideograph (the reference asks LangSegment for "zh", which is not available here, so kanji-only Japanese
 text loads it too).  Either sets tts_config.cnroberta, so a frontend written as
 `lambda t: get_phones_and_bert(t, tts.tts_config)` gets device BERT features; without the directory one warning is
-logged and bert2 stays zeros.  What else sits in front of the hot path in the reference -- G2P text frontends and audio
-file decoding -- is OUT OF SCOPE of this build (CPU string processing and third-party
-packages not installable here).  Their *outputs* enter through the same caches the reference keeps:
-    cache_spk_audio(path, ge=...)  or  cache_spk_audio(path, audio=<model-rate waveform>[, sv_emb=<ERes2Net embedding>])
-                                   (spectrogram + get_ge on the device, and for v2Pro / v2ProPlus without sv_emb the
-                                   ERes2NetV2 embedding as well; the reference: TTS.py:1346, 1576)
+logged and bert2 stays zeros.  Reference audio given as a path that names an existing WAV file (PCM or IEEE float, mono
+or stereo) is read as TTS._load_audio reads it: the container parsed on the host, the samples converted to fp32 mono on
+the device (wavio.py), so infer("spk.wav", "prompt.wav", ...) works as in the reference.  What else sits in front of the
+hot path in the reference -- G2P text frontends and decoding compressed audio (mp3, ogg, flac) -- is OUT OF SCOPE of this
+build (CPU string processing and third-party packages not installable here).  Their
+*outputs* enter through the same caches the reference keeps:
+    cache_spk_audio(path)  or  cache_spk_audio(path, ge=...)  or
+    cache_spk_audio(path, audio=<waveform>[, sample_rate=<model rate>][, sv_emb=<ERes2Net embedding>])
+                                   (resampling to the model rate, spectrogram + get_ge on the device, and for v2Pro /
+                                   v2ProPlus without sv_emb the ERes2NetV2 embedding as well; the reference: TTS.py:1346,
+                                   1576)
+    cache_prompt_audio(path, text[, phones1=..., bert1=...])  or
     cache_prompt_audio(path, text, prompt=... | ssl_content=<CN-HuBERT features> | audio=<waveform>[, sample_rate=16000],
                        phones1=..., bert1=...)
                                    (resampling + CN-HuBERT + extract_latent on the device; TTS.py:1391, 1556)
@@ -241,10 +247,11 @@ class TTS:
         """fn(text) -> (phones2 list[int], word2ph dict, bert2 [P,1024] tensor, norm_text)"""
         self._text_frontend = fn
 
-    def cache_spk_audio(self, spk_audio_paths, sovits_model=None, ge=None, audio=None, sv_emb=None):
+    def cache_spk_audio(self, spk_audio_paths, sovits_model=None, ge=None, audio=None, sv_emb=None, sample_rate=None):
         """TTS.py:1346-1389.  Either the finished embedding `ge` [1, gin, 1], or the reference waveform `audio`
-        (mono fp32 at the model rate, what TTS._load_audio + _resample give): then the spectrogram (TTS._get_spec) and
-        get_ge run on the device.  v2Pro / v2ProPlus add the ERes2Net embedding sv_emb [1, 20480]: the one passed, else the
+        (mono fp32 at `sample_rate`, None: the model rate; resampled to the model rate on the device, what TTS._load_audio
+        + _resample give), or neither when the key names an existing WAV file, which is then read (wavio.load_wav) and
+        resampled to the model rate: then the spectrogram (TTS._get_spec) and get_ge run on the device.  v2Pro / v2ProPlus add the ERes2Net embedding sv_emb [1, 20480]: the one passed, else the
         one this path's cache entry holds, else ERes2NetV2 on the device (16 kHz resample + fbank + forward3) from
         models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, kept loaded only when always_load_sv is set.  Without that
         checkpoint ge has no sv term (a warning says so).  The entry keeps the sv_emb, so another SoVITS model reuses it.
@@ -252,23 +259,26 @@ class TTS:
         A list of keys caches many speakers in one call (what the reference's cache_spk_audio(*paths) does): `audio` a list
         with one waveform per key, `ge` / `sv_emb` None or lists of the same length (None entries allowed).  ERes2NetV2 is
         loaded once and runs every clip that needs an sv_emb in one batched pass; each entry equals what a single-key call
-        gives.  Any other key (a str, a tuple) is one key, as before."""
+        gives; `sample_rate` is then one rate for all or a list, and keys with neither audio nor ge that name WAV files
+        are read in one packed pass (wavio.load_wavs).  Any other key (a str, a tuple) is one key, as before."""
         if isinstance(spk_audio_paths, list):
-            return self._cache_spk_batch(spk_audio_paths, sovits_model, ge, audio, sv_emb)
+            return self._cache_spk_batch(spk_audio_paths, sovits_model, ge, audio, sv_emb, sample_rate)
         sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
         entry = self.spk_audio_cache.get(spk_audio_paths)
         if ge is None:
             if audio is None:
-                raise NotImplementedError("decoding / resampling audio files is outside this build's scope; pass "
-                                          "ge=[1, gin, 1], or audio=<waveform> (+ sv_emb=[1, 20480])")
+                path = self._wav_file(spk_audio_paths)
+                if path is None:
+                    raise NotImplementedError("%r is no existing WAV file, and decoding / resampling audio files is outside "
+                                              "this build's scope; pass ge=[1, gin, 1], or audio=<waveform> (+ sv_emb=[1, "
+                                              "20480])" % (spk_audio_paths,))
+                from .wavio import load_wav
+                audio, sample_rate = load_wav(path, self.tts_config.device)
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
             sovits = self.sovits_models[sovits_model]
             vq = sovits.vq_model
-            audio = audio.to(self.tts_config.device).float().reshape(1, -1)
-            peak = audio.abs().max()
-            if peak > 1:                       # TTS.py:1586-1588
-                audio = audio / min(2, float(peak))
+            audio = self._spk_wave(audio, sample_rate, self._model_rate(sovits))
             if sv_emb is None and getattr(vq, "is_v2pro", False):
                 if entry is not None and entry.get("sv_emb") is not None:
                     sv_emb = entry["sv_emb"]
@@ -294,29 +304,32 @@ class TTS:
             raise ValueError("%s has %d entries for %d keys" % (name, len(v), n))
         return list(v)
 
-    def _cache_spk_batch(self, keys, sovits_model, ge, audio, sv_emb):
+    def _cache_spk_batch(self, keys, sovits_model, ge, audio, sv_emb, sample_rate):
         n = len(keys)
         ges = self._per_key(ge, n, "ge", lambda v: v is None)
         svs = self._per_key(sv_emb, n, "sv_emb", lambda v: v is None)
         auds = self._per_key(audio, n, "audio", lambda v: v is None)
+        rates = self._per_key(sample_rate, n, "sample_rate", lambda v: v is None or isinstance(v, numbers.Integral))
+        files = {}
         for i in range(n):
             if ges[i] is None and auds[i] is None:
-                raise NotImplementedError("decoding / resampling audio files is outside this build's scope; key %d (%r) "
-                                          "needs ge=[1, gin, 1] or audio=<waveform>" % (i, keys[i]))
+                files[i] = self._wav_file(keys[i])
+                if files[i] is None:
+                    raise NotImplementedError("decoding / resampling audio files is outside this build's scope; key %d "
+                                              "(%r) needs ge=[1, gin, 1] or audio=<waveform>, or to name an existing WAV "
+                                              "file" % (i, keys[i]))
         sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
         todo = [i for i in range(n) if ges[i] is None]
         if todo:
+            if files:
+                from .wavio import load_wavs
+                for i, (w, sr) in zip(files, load_wavs(list(files.values()), self.tts_config.device)):
+                    auds[i], rates[i] = w, sr
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
             sovits = self.sovits_models[sovits_model]
             vq = sovits.vq_model
-            wav = {}
-            for i in todo:
-                a = torch.as_tensor(auds[i]).to(self.tts_config.device).float().reshape(1, -1)
-                peak = a.abs().max()
-                if peak > 1:                       # TTS.py:1586-1588
-                    a = a / min(2, float(peak))
-                wav[i] = a
+            wav = {i: self._spk_wave(auds[i], rates[i], self._model_rate(sovits)) for i in todo}
             if getattr(vq, "is_v2pro", False):
                 need = []
                 for i in todo:
@@ -339,6 +352,23 @@ class TTS:
             entry["ge"][sovits_model] = ges[i].to(self.tts_config.device)
             if svs[i] is not None:
                 entry["sv_emb"] = torch.as_tensor(svs[i]).to(self.tts_config.device).float().reshape(1, -1)
+
+    @staticmethod
+    def _wav_file(key):
+        """key when it is a path (str or os.PathLike) naming an existing file, read as WAV; None for any other key"""
+        return key if isinstance(key, (str, os.PathLike)) and os.path.isfile(key) else None
+
+    def _spk_wave(self, audio, sample_rate, rate):
+        """TTS._get_spec's waveform: audio at sample_rate (None: already at `rate`) -> fp32 [1, n] on the device at the
+        model rate `rate` (sv.resample when the rates differ), then peak-normalised"""
+        a = torch.as_tensor(audio).to(self.tts_config.device).float().reshape(1, -1)
+        if sample_rate is not None and int(sample_rate) != rate:
+            from .sv import resample
+            a = resample(a, int(sample_rate), rate, self.tts_config.device).reshape(1, -1)
+        peak = a.abs().max()
+        if peak > 1:                       # TTS.py:1586-1588
+            a = a / min(2, float(peak))
+        return a
 
     @staticmethod
     def _model_rate(sovits) -> int:
@@ -371,21 +401,24 @@ class TTS:
 
     def verify_speaker(self, speaker1_audio, speaker2_audio) -> float:
         """TTS.py:1205-1245: cosine similarity (eps 1e-6) of two speakers' ERes2NetV2 embeddings.  Each argument is a
-        cache_spk_audio key whose entry holds an sv_emb, or a mono fp32 waveform at the model rate (that of the first
-        loaded SoVITS model, 32 kHz when none is loaded), peak-normalised here as TTS._get_spec does."""
+        cache_spk_audio key whose entry holds an sv_emb, a path that is no cached key and names an existing WAV file (read
+        and resampled to the model rate as cache_spk_audio does; nothing is cached), or a mono fp32 waveform at the model
+        rate (that of the first loaded SoVITS model, 32 kHz when none is loaded), peak-normalised here as TTS._get_spec
+        does."""
+        rate = self._model_rate(next(iter(self.sovits_models.values()))) if self.sovits_models else 32000
+
         def emb(a):
             if isinstance(a, (str, Path)):
+                path = None if a in self.spk_audio_cache else self._wav_file(a)
+                if path is not None:
+                    from .wavio import load_wav
+                    return self._sv_embed(self._spk_wave(*load_wav(path, self.tts_config.device), rate), rate)
                 e = self.spk_audio_cache.get(a, {}).get("sv_emb")
                 if e is None:
                     raise NotImplementedError("decoding / resampling audio files is outside this build's scope; cache %r "
                                               "with cache_spk_audio(audio=...) first, or pass its waveform" % (a,))
                 return e.to(self.tts_config.device).float().reshape(1, -1)
-            w = torch.as_tensor(a).to(self.tts_config.device).float().reshape(1, -1)
-            peak = w.abs().max()
-            if peak > 1:
-                w = w / min(2, float(peak))
-            rate = self._model_rate(next(iter(self.sovits_models.values()))) if self.sovits_models else 32000
-            return self._sv_embed(w, rate)
+            return self._sv_embed(self._spk_wave(a, None, rate), rate)
         try:
             e1, e2 = emb(speaker1_audio), emb(speaker2_audio)
             return float(torch.cosine_similarity(e1, e2, dim=-1, eps=1e-6).item())
@@ -398,18 +431,30 @@ class TTS:
         transposed as in TTS._get_prompt), or `audio`, the prompt waveform as mono fp32 at 16 kHz ([n] or [1, n]): then
         CN-HuBERT (TTS._get_prompt: + 0.3 s of zeros) and extract_latent run on the device.  CN-HuBERT is loaded from
         models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Audio at another
-        `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample).
+        `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample).  With none of
+        prompt / ssl_content / audio, a key that names an existing WAV file is read (wavio.load_wav) and takes that path at
+        the file's rate; phones1 (and bert1) then come from the text frontend when not given, as the reference's
+        get_phones_and_bert(prompt_audio_text) (TTS.py:1424).
 
         A list of keys caches many prompts in one call (the reference's list form): `audio` a list with one waveform per
         key, `prompt_audio_texts` one str for all or a list, `phones1` one list[int] for all or a list of them, `bert1`
-        None or a list, `sample_rate` one int or a list.  CN-HuBERT is loaded once and runs every clip in one batched pass,
-        then extract_latent runs per clip; each entry equals what a single-key call gives.  Lengths and empty texts are
-        checked before any device work.  Any other key (a str, a tuple) is one key, as before."""
+        None or a list, `sample_rate` one int or a list.  A key whose audio is None (or every key, without audio) that
+        names an existing WAV file is read, all such files in one packed pass; when every key is read from a file,
+        phones1 may be left out and comes from the text frontend.  CN-HuBERT is loaded once and runs every clip in one
+        batched pass, then extract_latent runs per clip; each entry equals what a single-key call gives.  Lengths and
+        empty texts are checked before any device work.  Any other key (a str, a tuple) is one key, as before."""
         if isinstance(prompt_audio_paths, list):
             return self._cache_prompt_batch(prompt_audio_paths, prompt_audio_texts, prompt, phones1, bert1, ssl_content,
                                             sovits_model, audio, sample_rate)
         if not prompt_audio_texts:
             raise ValueError("prompt_audio_text must not be empty")
+        path = self._wav_file(prompt_audio_paths) if prompt is None and ssl_content is None and audio is None else None
+        if path is not None:
+            if phones1 is None and self._text_frontend is not None:      # TTS.py:1424
+                phones1, _, fb, _ = self._phones_and_bert(prompt_audio_texts)
+                bert1 = fb if bert1 is None else bert1
+            from .wavio import load_wav
+            audio, sample_rate = load_wav(path, self.tts_config.device)
         if prompt is None and ssl_content is None and audio is not None:
             if int(sample_rate) != 16000:
                 from .sv import resample
@@ -455,16 +500,34 @@ class TTS:
         for i, t in enumerate(texts):
             if not t:
                 raise ValueError("prompt_audio_texts[%d] must not be empty" % i)
-        if audio is None:
-            raise NotImplementedError("decoding / resampling audio files and G2P are outside this build's scope; a list of "
-                                      "keys needs audio=[one mono fp32 waveform per key] and phones1")
-        auds = self._per_key(audio, n, "audio", lambda v: False)
+        auds = self._per_key(audio, n, "audio", lambda v: v is None)
+        files = {}
+        for i in range(n):
+            if auds[i] is None:
+                files[i] = self._wav_file(keys[i])
+                if files[i] is None and audio is None:
+                    raise NotImplementedError("decoding / resampling audio files and G2P are outside this build's scope; a "
+                                              "list of keys needs audio=[one mono fp32 waveform per key] and phones1, or "
+                                              "keys that name existing WAV files")
+                if files[i] is None:
+                    raise NotImplementedError("decoding / resampling audio files is outside this build's scope; key %d (%r) "
+                                              "needs audio=<waveform> or to name an existing WAV file" % (i, keys[i]))
+        fronts = None
         if phones1 is None:
-            raise NotImplementedError("G2P is outside this build's scope; pass phones1=list[int] or one list[int] per key")
+            if len(files) < n or self._text_frontend is None:
+                raise NotImplementedError("G2P is outside this build's scope; pass phones1=list[int] or one list[int] per key")
+            fronts = [self._phones_and_bert(t) for t in texts]        # TTS.py:1424
+            phones1 = [f[0] for f in fronts]
         phones = self._per_key(phones1, n, "phones1",
                                lambda v: isinstance(v, (list, tuple)) and (not v or isinstance(v[0], numbers.Integral)))
         berts = self._per_key(bert1, n, "bert1", lambda v: v is None)
+        if fronts is not None:
+            berts = [f[2] if b is None else b for f, b in zip(fronts, berts)]
         rates = self._per_key(sample_rate, n, "sample_rate", lambda v: isinstance(v, numbers.Integral))
+        if files:
+            from .wavio import load_wavs
+            for i, (w, sr) in zip(files, load_wavs(list(files.values()), self.tts_config.device)):
+                auds[i], rates[i] = w, sr
         wavs = []
         for i, a in enumerate(auds):
             a = torch.as_tensor(a)

@@ -444,6 +444,30 @@ size_t gsv_sv_resample_workspace(int orig_sr, int new_sr);
  * [gsv_sv_resample_length(n, orig_sr, new_sr)].  Needs no model handle. */
 int gsv_sv_resample(const float* x, int n_samples, int orig_sr, int new_sr, float* y, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* Reference-audio files: the samples of a WAV data chunk, copied to the device as they are in the file (interleaved
+ * little-endian frames), -> fp32 mono, what TTS._load_audio gets from av.AudioResampler(format='flt', layout='mono')
+ * (gsv_tts/TTS.py:1811-1823).  u8 (x - 128) / 2^7, s16 x / 2^15, packed s24 x / 2^23, s32 x / 2^31, f32 as is, f64 cast
+ * to float; 1 or 2 channels, stereo mixed as (L + R) * sqrt(1/2).  Needs no model handle, allocates
+ * nothing, reads no alignment into pcm.  The host parses the RIFF container (gsv_tts_lite_amd/wavio.py). */
+#define GSV_PCM_U8 0
+#define GSV_PCM_S16 1
+#define GSV_PCM_S24 2
+#define GSV_PCM_S32 3
+#define GSV_PCM_F32 4
+#define GSV_PCM_F64 5
+/* pcm: pcm_bytes device bytes holding n_frames frames of `channels` samples of `format` from byte 0 -> out fp32
+ * [n_frames].  GSV_ERR_ARG for an unknown format, channels outside 1..2, n_frames < 1 or frames past pcm_bytes. */
+int gsv_wav_to_mono(const void* pcm, size_t pcm_bytes, int n_frames, int format, int channels, float* out, void* stream);
+/* one clip of gsv_wav_to_mono_batch: its frames start at byte_offset of the packed pcm */
+typedef struct gsv_wav_clip {
+    int64_t byte_offset;
+    int32_t n_frames;
+    int16_t format;     /* GSV_PCM_* */
+    int16_t channels;   /* 1 or 2 */
+} gsv_wav_clip;
+/* up to GSV_AUX_MAX_CLIPS clips (a HOST array) in one launch: out holds clip i's [n_frames_i] at offset
+ * sum_{j<i} n_frames_j, bit-identical to gsv_wav_to_mono on that clip.  GSV_ERR_ARG names the first bad clip. */
+int gsv_wav_to_mono_batch(const void* pcm, size_t pcm_bytes, const gsv_wav_clip* clips, int n_clips, float* out, void* stream);
 /* fbank frames of a waveform of n_samples at sample_rate once it is at 16 kHz: 1 + (n16 - 400) / 160, 0 if n16 < 400 */
 int gsv_sv_frames(gsv_sv* h, int n_samples, int sample_rate);
 /* device bytes of the caller-owned workspace of gsv_sv_embed over n_samples at sample_rate; it also covers
