@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
+#include <cstdint>
 #include <map>
 #include <mutex>
 #include <unordered_map>
@@ -150,7 +152,10 @@ struct T2SLayer {
 
 struct T2SStateX : gsv_t2s_state {      // the caller's state + what the library keeps beside it
     int32_t* eos_host = nullptr;         // host-mapped mirror of eos_at (gsv_t2s_set_eos_mirror)
+    u32x4* tab = nullptr;                // per-slot sampling table [batch] (gsv_t2s_set_slot_sampling)
 };
+static_assert(sizeof(gsv_t2s_slot_sampling) == sizeof(u32x4) * kSlotSamplingWords, "the token kernel reads an entry as two 16-byte words");
+inline u32x4* tab_of(const gsv_t2s_state& s) { return static_cast<const T2SStateX&>(s).tab; }
 inline int32_t* eos_host_of(const gsv_t2s_state& s) { return static_cast<const T2SStateX&>(s).eos_host; }   // every state here is a T2SBound's
 
 struct T2SBound {
@@ -506,8 +511,9 @@ int t2s_token(gsv_t2s* h, const gsv_t2s_state& s, int advance, hipStream_t st) {
     a.pre_tokens = s.pre_tokens; a.seen = s.seen; a.step = s.step; a.eos_at = s.eos_at; a.eos_host = eos_host_of(s); a.emb = h->emb_audio;
     a.pe = h->pe_audio; a.xcur = h->xcur; a.T = s.max_kv; a.V = h->cfg.vocab; a.eos = h->cfg.eos; a.n_pos = h->cfg.n_pos;
     a.advance = advance;
-    a.logits = s.logits; a.fctl = s.fctl;
-    hipLaunchKernelGGL(t2s_token_kernel, dim3(s.batch), dim3(256), 0, st, a);
+    a.logits = s.logits; a.fctl = s.fctl; a.tab = tab_of(s);
+    if (a.tab) hipLaunchKernelGGL(t2s_token_kernel<true>, dim3(s.batch), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(t2s_token_kernel<false>, dim3(s.batch), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
     return GSV_OK;
 }
@@ -919,6 +925,7 @@ struct MoveArgs {
     const int64_t *s_kv, *s_x, *s_pre, *s_ovr; const int32_t *s_step, *s_eos; const float *s_logits, *s_hidden; const unsigned char* s_seen;
     int64_t *d_kv, *d_x, *d_pre, *d_ovr; int32_t *d_step, *d_eos, *d_eos_host; float *d_logits, *d_hidden; unsigned char* d_seen;
     TokPart* tokpart;                 // ONE array per handle, indexed by slot: source and destination rows may overlap
+    const u32x4* s_tab; u32x4* d_tab; // the two states' sampling tables (both or neither)
 };
 __global__ __launch_bounds__(256) void t2s_move_kv_kernel(MoveArgs a) {
     const int lh = blockIdx.x, r = blockIdx.y, l = lh / kH, hd = lh % kH;
@@ -951,6 +958,18 @@ __global__ __launch_bounds__(256) void t2s_move_state_kernel(MoveArgs a) {
         a.d_kv[s] = a.s_kv[ss]; a.d_x[s] = a.s_x[ss]; a.d_step[s] = a.s_step[ss]; a.d_eos[s] = a.s_eos[ss]; a.d_ovr[s] = a.s_ovr[ss];
         eos_publish(a.d_eos_host, s, a.s_eos[ss]);
     }
+    if (a.s_tab != nullptr && tid < kSlotSamplingWords) a.d_tab[kSlotSamplingWords * s + tid] = a.s_tab[kSlotSamplingWords * ss + tid];
+}
+
+// entries of a bound state's sampling table, written from the kernel arguments (gsv_t2s_put_slot_sampling)
+struct PutSamplingArgs {
+    short slot[kAdoptMax];
+    u32x4 e[kAdoptMax][kSlotSamplingWords];
+    u32x4* tab;
+};
+__global__ __launch_bounds__(64) void t2s_put_sampling_kernel(PutSamplingArgs a) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (tid < kSlotSamplingWords) a.tab[kSlotSamplingWords * a.slot[r] + tid] = a.e[r][tid];
 }
 
 }  // namespace
@@ -1111,6 +1130,7 @@ int gsv_t2s_bind_state(gsv_t2s* h, const gsv_t2s_state* st) {
     t2s_drop_graphs(b);
     static_cast<gsv_t2s_state&>(b.st) = *st;
     b.st.eos_host = nullptr;
+    b.st.tab = nullptr;
     t2s_free_staging(b);
     const size_t B = (size_t)st->batch;
     HIPCHK(gsv_dev_malloc(&b.sg_kv, 8 * B)); HIPCHK(gsv_dev_malloc(&b.sg_x, 8 * B));
@@ -1265,7 +1285,10 @@ int gsv_t2s_move_slots(gsv_t2s* h, int batch_dst, const int32_t* slots_dst, int 
         for (int j = 0; j < i; ++j)
             if (slots_dst[j] == slots_dst[i] || slots_src[j] == slots_src[i]) return fail(GSV_ERR_ARG, "move_slots: slot listed twice");
     }
+    if (sb->st.tab && !d->st.tab)
+        return fail(GSV_ERR_ARG, "move_slots: batch %d has a per-slot sampling table and batch %d has none: the moved slots' parameters would be lost", batch_src, batch_dst);
     MoveArgs a;
+    a.s_tab = d->st.tab ? sb->st.tab : nullptr; a.d_tab = d->st.tab;
     a.ks = (const unsigned char*)sb->st.k_cache; a.vs = (const unsigned char*)sb->st.v_cache; a.kd = (unsigned char*)d->st.k_cache; a.vd = (unsigned char*)d->st.v_cache;
     a.Bs = batch_src; a.Ts = sb->st.max_kv; a.Bd = batch_dst; a.Td = d->st.max_kv; a.esz = h->cfg.dtype == GSV_F32 ? 4 : 2; a.V = h->cfg.vocab; a.n = nrows;
     a.s_kv = sb->st.kv_len; a.s_x = sb->st.x_len; a.s_pre = sb->st.pre_tokens; a.s_ovr = sb->st.tok_override; a.s_step = sb->st.step; a.s_eos = sb->st.eos_at;
@@ -1351,6 +1374,40 @@ int gsv_t2s_set_eos_mirror(gsv_t2s* h, int batch, int32_t* host_mapped) {
     b->st.eos_host = host_mapped;
     // the captured steps hold their kernel arguments by value
     t2s_drop_graphs(*b);
+    return GSV_OK;
+}
+
+int gsv_t2s_set_slot_sampling(gsv_t2s* h, int batch, gsv_t2s_slot_sampling* table) {
+    if (!h || !h->finalized) return fail(GSV_ERR_STATE, "handle not finalized");
+    T2SBound* b = t2s_find(h, batch);
+    if (!b) return fail(GSV_ERR_STATE, "no state bound for batch %d", batch);
+    if ((uintptr_t)table % 16 != 0) return fail(GSV_ERR_ARG, "set_slot_sampling: the table must be 16-byte aligned");
+    if (b->st.tab == (u32x4*)table) return GSV_OK;
+    b->st.tab = (u32x4*)table;
+    // the captured steps hold their kernel (with / without a table) and its arguments by value
+    t2s_drop_graphs(*b);
+    return GSV_OK;
+}
+
+int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const gsv_t2s_slot_sampling* entries, int nrows, void* stream) {
+    if (!h || !h->finalized) return fail(GSV_ERR_STATE, "handle not finalized");
+    T2SBound* b = t2s_find(h, batch);
+    if (!b) return fail(GSV_ERR_STATE, "no state bound for batch %d", batch);
+    if (!b->st.tab) return fail(GSV_ERR_STATE, "put_slot_sampling: batch %d has no per-slot sampling table (gsv_t2s_set_slot_sampling)", batch);
+    if (!slots || !entries || nrows < 1) return fail(GSV_ERR_ARG, "put_slot_sampling: need slots and entries (host arrays)");
+    for (int i = 0; i < nrows; ++i) {
+        if (slots[i] < 0 || slots[i] >= batch) return fail(GSV_ERR_ARG, "put_slot_sampling: slot %d out of range", (int)slots[i]);
+        if (entries[i].sample_mode != 0 && entries[i].sample_mode != 2)
+            return fail(GSV_ERR_ARG, "put_slot_sampling: entry %d has sample_mode %d (0 = greedy, 2 = device sampling)", i, (int)entries[i].sample_mode);
+    }
+    PutSamplingArgs a;
+    a.tab = b->st.tab;
+    for (int r0 = 0; r0 < nrows; r0 += kAdoptMax) {
+        const int n = std::min(kAdoptMax, nrows - r0);
+        for (int i = 0; i < n; ++i) { a.slot[i] = (short)slots[r0 + i]; memcpy(a.e[i], &entries[r0 + i], sizeof(gsv_t2s_slot_sampling)); }
+        hipLaunchKernelGGL(t2s_put_sampling_kernel, dim3(n), dim3(64), 0, S(stream), a);
+    }
+    HIPCHK(hipGetLastError());
     return GSV_OK;
 }
 

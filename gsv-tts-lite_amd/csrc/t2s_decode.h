@@ -1015,7 +1015,12 @@ struct TokenArgs {
     const float* logits;     // [B][V] penalised logits of the pending sample (device sampling, ctl[0] == 2)
     const float* fctl;       // fctl[1] = temperature
     int32_t* eos_host;       // null, or a host-mapped mirror of eos_at
+    const u32x4* tab;        // null, or the per-slot sampling table (gsv_t2s_set_slot_sampling): two 16-byte words per slot
 };
+
+// One entry of the per-slot sampling table as the token kernel reads it: {sample_mode, top_k, temperature, top_p} and
+// {seed_lo, seed_hi, -, -} (gsv_t2s_slot_sampling, include/gsv_tts_hip.h).
+constexpr int kSlotSamplingWords = 2;
 
 // Counter-based uniform in (0, 1): one draw per (seed, slot, absolute position, vocabulary entry).  The
 // reference draws Exp(1) noise from torch's generator (GPT/utils.py:56-59); a device sampler cannot share
@@ -1166,13 +1171,21 @@ __device__ __forceinline__ int t2s_sample_wave(const float* __restrict__ lg, int
     return bi < V ? bi : 0;
 }
 
+// TAB: slot b's mode and sampling parameters come from the table entry instead of ctl[0], ctl[4..6], fctl[1..2] (ctl[0] == 1, host
+// tokens, stays a whole-state mode); greedy and sampled slots then sit side by side in one launch.  The two entry words are loads
+// whose address depends on nothing: they are issued first.  Without a table the kernel is the <false> instantiation, which reads ctl / fctl only.
+template <bool TAB>
 static __global__ __launch_bounds__(256) void t2s_token_kernel(TokenArgs a) {
     __shared__ int s_tok;
     const int b = blockIdx.x, tid = threadIdx.x;
-    // ---- device sampling (ctl[0] == 2): temperature, top-k with the reference's tie rule, then the
+    u32x4 e0 = {}, e1 = {};
+    if constexpr (TAB) { e0 = a.tab[kSlotSamplingWords * b]; e1 = a.tab[kSlotSamplingWords * b + 1]; }
+    const int ctl0 = a.ctl[0];
+    const int mode = TAB && ctl0 != 1 ? (int)e0[0] : ctl0;
+    // ---- device sampling (mode 2): temperature, top-k with the reference's tie rule, then the
     // exponential race of GPT/utils.py:56-59 as a Gumbel argmax: argmax p/q, q ~ Exp(1)  ==  argmax (x - log q)
     int sampled = -1;
-    if (a.ctl[0] == 2 && tid < 64) {
+    if (mode == 2 && tid < 64) {
         const float* lg = a.logits + (size_t)b * a.V;
         const uint32_t pos = (uint32_t)a.kv_len[b], stp = (uint32_t)a.step[b];
         // the noise stream of this sequence: tok_override[b] - 1 when the caller set one (> 0; continuous batching keys it
@@ -1180,14 +1193,17 @@ static __global__ __launch_bounds__(256) void t2s_token_kernel(TokenArgs a) {
         // else the slot index
         const int64_t sid = a.tok_override[b];
         const uint32_t stream = sid > 0 ? (uint32_t)(sid - 1) : (uint32_t)b;
-        sampled = a.V <= 64 * 17 ? t2s_sample_wave<17>(lg, a.V, a.fctl[1], a.fctl[2], a.ctl[4], (uint32_t)a.ctl[5], (uint32_t)a.ctl[6], stream, pos, stp)
-                                 : t2s_sample_wave<32>(lg, a.V, a.fctl[1], a.fctl[2], a.ctl[4], (uint32_t)a.ctl[5], (uint32_t)a.ctl[6], stream, pos, stp);
+        const float temperature = TAB ? __uint_as_float(e0[2]) : a.fctl[1], top_p = TAB ? __uint_as_float(e0[3]) : a.fctl[2];
+        const int k = TAB ? (int)e0[1] : a.ctl[4];
+        const uint32_t seed_lo = TAB ? e1[0] : (uint32_t)a.ctl[5], seed_hi = TAB ? e1[1] : (uint32_t)a.ctl[6];
+        sampled = a.V <= 64 * 17 ? t2s_sample_wave<17>(lg, a.V, temperature, top_p, k, seed_lo, seed_hi, stream, pos, stp)
+                                 : t2s_sample_wave<32>(lg, a.V, temperature, top_p, k, seed_lo, seed_hi, stream, pos, stp);
     }
     if (tid == 0) {
         int tok;
-        if (a.ctl[0] == 2) {
+        if (mode == 2) {
             tok = sampled;
-        } else if (a.ctl[0] != 0) {
+        } else if (mode != 0) {
             tok = (int)a.tok_override[b];
         } else {
             float bv = -INFINITY;

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import slot_sampling as SS
 
 
 class Bucket:
@@ -427,6 +428,40 @@ class Text2SemanticDecoder:
     def _flush(self, batch):
         N.check(N.lib().gsv_t2s_flush(self._h, batch, N.current_stream_ptr(self.device)))
 
+    def _bind_sampling(self, rt):
+        """the per-slot sampling table of a bound state (gsv_t2s_set_slot_sampling): [B] entries of 8 words, all greedy at first"""
+        if rt.get("samp") is None:
+            rt["samp"] = torch.zeros(rt["batch"], 8, dtype=torch.int32, device=self.device)
+        else:
+            rt["samp"].zero_()
+        torch.cuda.synchronize(self.device)     # the state's captured steps go: none of them may be running
+        N.check(N.lib().gsv_t2s_set_slot_sampling(self._h, rt["batch"], rt["samp"].data_ptr()))
+        self._samp_bound = self._samp_bound + [rt]
+        self.sampling_binds = getattr(self, "sampling_binds", 0) + 1
+
+    def _unbind_sampling(self):
+        torch.cuda.synchronize(self.device)
+        for rt in self._samp_bound:
+            N.check(N.lib().gsv_t2s_set_slot_sampling(self._h, rt["batch"], None))
+        self._samp_bound = []
+
+    def _put_sampling(self, batch, slots, requests):
+        """the slots take these requests: their table entries, on the current stream (a scalar call has no table: nothing)"""
+        samp = self._samp
+        if samp is None or not len(slots):
+            return
+        n = len(slots)
+        sl = (ctypes.c_int32 * n)(*[int(v) for v in slots])
+        en = (N.SlotSampling * n)(*[N.SlotSampling(*samp.entry(int(c))) for c in requests])
+        N.check(N.lib().gsv_t2s_put_slot_sampling(self._h, batch, sl, en, n, N.current_stream_ptr(self.device)))
+
+    def _stream_id(self, c):
+        """tok_override of a slot that takes request c under device sampling: its noise stream + 1"""
+        return c + 1 if self._samp is None else self._samp.stream(c)
+
+    _samp = None            # the RequestSampling of the infer_batched call that is running, or None (one set per call)
+    _samp_bound = []        # states whose table is bound for it
+
     def _set_ctl(self, rt, mode, suppress_steps, rep_enabled, rep, top_k=0, temperature=1.0, seed=0, top_p=1.0,
                  suppress_first=False):
         """mode 0 = greedy on device, 2 = device sampling (1, host-sampled tokens through tok_override, is the C ABI's and unused here); suppress_first: the
@@ -672,7 +707,7 @@ class Text2SemanticDecoder:
                 # copy blocks the host until its stream gets there -- it must not sit behind the wait on the steps
                 xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in rq], [y[c] for c in rq], [bert_feature[c] for c in rq])
                 sl = torch.tensor([i for i, _, _ in group], dtype=torch.int32, device=dev)
-                ids = torch.tensor([c + 1 for _, c, _ in group], dtype=torch.int64, device=dev)
+                ids = torch.tensor([self._stream_id(c) for _, c, _ in group], dtype=torch.int64, device=dev)
                 side.wait_event(ev)
                 self.prefill_slots_staged(B, sl, xy1, xl1, yl1, side.cuda_stream)
                 done = torch.cuda.Event()
@@ -701,6 +736,7 @@ class Text2SemanticDecoder:
             if stream_by_request:       # device sampling: the joined slots draw from their requests' noise streams
                 rt["tok_override"].index_copy_(0, sl.long(), _keep[3])
                 _keep[3].record_stream(main)
+            self._put_sampling(B, [i for i, _, _ in group], [c for _, c, _ in group])
             for i, _, n_new in group:
                 state[i], steps[i], start[i], joined[i] = LIVE, 0, n_new, window
             inflight.clear()
@@ -787,6 +823,11 @@ class Text2SemanticDecoder:
         # tail compaction: bound BEFORE the first step (binding may re-allocate the handle's scratch), largest first
         tails = [t for t in (self._tail_state(lv, cap) for lv in sorted(set(self.tail_levels), reverse=True) if lv < B) if t is not None]
         B0 = B
+        if self._samp is not None:
+            # compaction carries a slot's entry to the tail state's table (gsv_t2s_move_slots).  The ahead state has none: it is
+            # never stepped, and an adopted request's first token is drawn by the token kernel of the adopting state
+            for t in tails:
+                self._bind_sampling(t)
         for k in ("ctl", "fctl"):
             sh[k].copy_(rt[k])          # the prompt pass's first logits obey the same control words
         if getattr(self, "_refill_stream", None) is None:
@@ -920,7 +961,8 @@ class Text2SemanticDecoder:
             if not take:
                 return
             self.adopt_slots(B, [i for i, _, _, _ in take], sh["batch"], [s_ for _, s_, _, _ in take],
-                             [c + 1 for _, _, c, _ in take] if stream_by_request else None)
+                             [self._stream_id(c) for _, _, c, _ in take] if stream_by_request else None)
+            self._put_sampling(B, [i for i, _, _, _ in take], [c for _, _, c, _ in take])
             ev = torch.cuda.Event()
             ev.record(main)
             adopted_ev[0] = ev
@@ -1011,8 +1053,16 @@ class Text2SemanticDecoder:
     def infer_batched(self, x: List[torch.Tensor], y: List[torch.Tensor], bert_feature: List[torch.Tensor],
                       top_k: int = 15, top_p: float = 1.0, temperature: float = 1.0,
                       repetition_penalty: float = 1.35, check_interval: int = 5, generator=None,
-                      source=None, slots: int = None, on_finish=None, max_new_tokens=None, async_refill: bool = False):
+                      source=None, slots: int = None, on_finish=None, max_new_tokens=None, async_refill: bool = False,
+                      seed=None):
         """t2s_model.py:555-734: continuous batching over the slots of one batch-size family.
+
+        `top_k`, `top_p`, `temperature` and `seed` are scalars -- one set for the call, as in the reference -- or sequences
+        indexed like `x` (with `source`: by the GLOBAL request index): request i is then decoded with its own values, greedy
+        (top_k 1) and sampled requests side by side in the slots of one captured step (the per-slot sampling table,
+        gsv_t2s_set_slot_sampling).  With `seed` None the noise is keyed as in a scalar call: one seed drawn from `generator`,
+        stream = request index.  `seed[i]` given: request i draws from (seed[i], stream 0), so its tokens depend on its own
+        inputs, parameters and seed only.  All scalars and no seed: no table is bound, the call is the scalar one.
 
         `source` (engine.RequestSource) replaces "the next request is x[cur]" (:696-700) by "the next request is
         whatever the shared queue hands this rank": x / y / bert_feature are then the GLOBAL lists, the returned
@@ -1023,6 +1073,21 @@ class Text2SemanticDecoder:
         request i once it has produced that many tokens -- tested at the same 5-step cadence as EOS, cut exactly.
         `async_refill` (not in the reference, whose slots all wait while a refill's prompt pass runs, :696-722) runs the
         slot loop of `_infer_batched_staged` instead: same requests, same tokens per request, no stall."""
+        samp = SS.resolve(len(x), top_k, top_p, temperature, seed)
+        if samp is None:
+            return self._infer_batched_call(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval,
+                                            generator, source, slots, on_finish, max_new_tokens, async_refill)
+        self._samp = samp
+        try:
+            return self._infer_batched_call(x, y, bert_feature, 0, 1.0, 1.0, repetition_penalty, check_interval,
+                                            generator, source, slots, on_finish, max_new_tokens, async_refill)
+        finally:
+            self._samp = None
+            self._unbind_sampling()
+
+    def _infer_batched_call(self, x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval, generator,
+                            source, slots, on_finish, max_new_tokens, async_refill):
+        """infer_batched behind the resolution of its sampling arguments (`self._samp`: per request, or None: the scalars here)"""
         if async_refill and self.step_priority != 0 and not getattr(self, "_in_step_stream", False):
             # the slot loop on a stream of its own priority (the steps are a chain of short dependent launches: whatever a
             # launch waits for behind a prompt pass's blocks is on the critical path, the prompt pass itself is not)
@@ -1033,7 +1098,7 @@ class Text2SemanticDecoder:
             self._in_step_stream = True
             try:
                 with torch.cuda.stream(self._step_stream):
-                    out = self.infer_batched(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval,
+                    out = self._infer_batched_call(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval,
                                              generator, source, slots, on_finish, max_new_tokens, async_refill)
             finally:
                 self._in_step_stream = False
@@ -1070,11 +1135,16 @@ class Text2SemanticDecoder:
         dev = self.device
         if actual == 0:
             return [], torch.zeros(0, dtype=torch.int64, device=dev)
-        mode, seed = self._sampling_mode(top_k, top_p, generator)
+        if self._samp is None:
+            mode, seed = self._sampling_mode(top_k, top_p, generator)
+        else:       # ctl[0] = 2 if any request samples (it gates the fused token step); the call's seed is drawn as a scalar call draws it
+            mode, seed = self._samp.begin(lambda: self._sampling_mode(0, None, generator)[1])
         if async_refill and self.refill_ahead > 0:
             # bound BEFORE the first prompt pass: binding a state may re-allocate the handle's per-slot scratch (pending tokens)
             self._ahead_state(max(1, min(self.refill_ahead, batch_size)), max(caps))
         self._set_ctl(rt, mode, 0, False, 1.0, top_k, temperature, seed, top_p)
+        if self._samp is not None:
+            self._bind_sampling(rt)
         rt["kv_len"].zero_()
         rt["x_len"].zero_()
         xy, xl, yl, x_lens_h, y_lens_h = self.embed_prompt([x[c] for c in first], [y[c] for c in first],
@@ -1091,7 +1161,8 @@ class Text2SemanticDecoder:
         rows = torch.arange(batch_size, device=dev)
         if mode == 2:       # device sampling: the noise stream of a slot is its REQUEST (placement-invariant samples)
             rt["tok_override"].zero_()
-            rt["tok_override"][:actual] = torch.tensor([c + 1 for c in first], dtype=torch.int64, device=dev)
+            rt["tok_override"][:actual] = torch.tensor([self._stream_id(c) for c in first], dtype=torch.int64, device=dev)
+        self._put_sampling(batch_size, range(actual), first)
         if async_refill:
             try:
                 loop = self._infer_batched_ahead if self.refill_ahead > 0 else self._infer_batched_staged
@@ -1193,5 +1264,6 @@ class Text2SemanticDecoder:
                 self.last_stats["refills"] += len(refill)
                 if mode == 2:
                     rt["tok_override"][torch.tensor([i for i, _ in refill], device=dev)] = \
-                        torch.tensor([c + 1 for _, c in refill], dtype=torch.int64, device=dev)
+                        torch.tensor([self._stream_id(c) for _, c in refill], dtype=torch.int64, device=dev)
+                self._put_sampling(batch_size, [i for i, _ in refill], req)
         return pred, torch.tensor(orig, device=dev)

@@ -50,6 +50,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from . import slot_sampling
 from . import subtitles as sub
 from .batchmath import balance_order, split_bounds
 from .stream import ChunkSplicer
@@ -935,7 +936,9 @@ class TTS:
                                           ",": 1.0, "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0,
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
-                      bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None):
+                      bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None):
+        """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
+        inherit its values); see Text2SemanticDecoder.infer_batched.  noise_scale and speed are per call."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
@@ -966,6 +969,8 @@ class TTS:
                     for c in cut_text(t, cut_minlen):
                         segs.append(c)
                         seg2orig.append(i)
+                sampling = {k: slot_sampling.per_segment(k, v, n, seg2orig) for k, v in
+                            (("top_k", top_k), ("top_p", top_p), ("temperature", temperature), ("seed", seed))}
                 eng = self._engine(t2s)     # None in a single process
                 if eng is not None:         # reference-speaker tensors exist on rank 0 only: ONE broadcast per new key
                     self._sync_speakers(prompt_audio_paths, prompt_audio_texts, spk_audio_paths, sovits_model)
@@ -985,16 +990,14 @@ class TTS:
                 if eng is None:
                     # staged refill: same tokens per request as the reference-order loop (greedy: rows are independent;
                     # sampling: the noise stream is the request's), no stall of the other slots on a prompt pass
-                    pred, orig_idx = t2s.infer_batched(ids, prompts, berts, top_k=top_k, top_p=top_p,
-                                                       temperature=temperature, repetition_penalty=repetition_penalty,
-                                                       async_refill=True)
+                    pred, orig_idx = t2s.infer_batched(ids, prompts, berts, repetition_penalty=repetition_penalty,
+                                                       async_refill=True, **sampling)
                     tokens = [None] * len(segs)
                     for p_, o in zip(pred, orig_idx.tolist()):
                         tokens[o] = p_
                 else:   # this rank's share of the segment queue (engine.py), then every rank learns every segment's tokens
-                    pred, orig_idx = eng.run_gpt(ids, prompts, berts, costs=[int(i.shape[0]) for i in ids], top_k=top_k, top_p=top_p,
-                                                 temperature=temperature, repetition_penalty=repetition_penalty,
-                                                 async_refill=True)
+                    pred, orig_idx = eng.run_gpt(ids, prompts, berts, costs=[int(i.shape[0]) for i in ids],
+                                                 repetition_penalty=repetition_penalty, async_refill=True, **sampling)
                     tokens = eng.exchange({int(o): p_ for p_, o in zip(pred, orig_idx.tolist())}, len(segs), dst=None)
                     eng._retire_cursors(None)
                 # TTS.py:705-716 sorts the COMPLETION-order list by length; completion order depends on slot timing (and on

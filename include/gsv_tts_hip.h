@@ -109,6 +109,33 @@ int gsv_t2s_unbind_state(gsv_t2s* h, int batch);
  * captured steps of this batch size. */
 int gsv_t2s_set_eos_mirror(gsv_t2s* h, int batch, int32_t* host_mapped);
 
+/* Optional: PER-SLOT sampling parameters for one bound state (continuous batching whose requests bring their own top_k / top_p /
+ * temperature / seed; the reference's batched loop has one set per call, t2s_model.py:555-734).  `table` is a caller-owned DEVICE
+ * array of `batch` entries, 16-byte aligned, or NULL to turn it off.  With a table the token step takes slot b's sample_mode
+ * (0 greedy | 2 device sampling) and parameters from table[b] instead of ctl[0], ctl[4..6], fctl[1..2]; suppress_steps,
+ * rep_enabled, suppress_first and the repetition penalty stay in ctl / fctl, and ctl[0] == 1 (host tokens) stays a whole-state
+ * mode that overrides the table.  The entries are read from device memory by every step, so one captured step serves any mix and
+ * an entry may change between two gsv_t2s_decode calls.  A slot's pending token is drawn by the token kernel of the NEXT step (or
+ * gsv_t2s_flush) of the state the slot lives in, so a request's entry has to be in place there before that step, wherever its
+ * prompt pass ran (gsv_t2s_prefill*, gsv_t2s_commit_slots, gsv_t2s_adopt_slots); gsv_t2s_move_slots carries a moved slot's entry
+ * to the destination's table (GSV_ERR_ARG when the source has a table and the destination has none).  GSV_STEP_FUSED_TOKEN keeps
+ * its meaning: the caller's promise that no slot samples.  Call after gsv_t2s_bind_state (which clears it); a change of the table
+ * pointer invalidates the captured steps of this batch size. */
+typedef struct {
+    int32_t sample_mode;    /* 0 greedy argmax | 2 device sampling */
+    int32_t top_k;          /* as ctl[4] */
+    float temperature;      /* as fctl[1] */
+    float top_p;            /* as fctl[2] */
+    int32_t seed_lo, seed_hi; /* as ctl[5], ctl[6]; the noise stream stays tok_override[slot] - 1, else the slot index */
+    int32_t reserved[2];    /* 0 */
+} gsv_t2s_slot_sampling;
+int gsv_t2s_set_slot_sampling(gsv_t2s* h, int batch, gsv_t2s_slot_sampling* table);
+/* Writes table[slots[r]] = entries[r] on `stream`; slots / entries are HOST arrays [nrows] that ride in the kernel arguments (no
+ * host-to-device copy between two decode windows).  GSV_ERR_STATE without a table; GSV_ERR_ARG for a slot out of range or a
+ * sample_mode other than 0 / 2. */
+int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const gsv_t2s_slot_sampling* entries, int nrows,
+                              void* stream);
+
 /* replaces process_single_data / process_batch_data (t2s_model.py:300-383): builds packed rows
  * [x_b | y_b | 0-pad] = text-emb + bert_proj + alpha_t*pe, audio-emb + alpha_a*pe.
  *   x_ids [nrows][lx_max], y_ids [nrows][ly_max], bert [nrows][lx_max][1024] (row-padded),
