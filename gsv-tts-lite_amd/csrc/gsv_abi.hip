@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -201,7 +202,6 @@ struct gsv_t2s {
     bool fp8 = false;              // GSV_FP8: e4m3 QKV / FFN weights in the batched step (everything else as GSV_BF16)
     int batched_min = 0;           // batch size from which the step is the batched chain
     int nt_from_layer = 0x7fffffff; // fp32 handles: layers from this one on load their weights non-temporally (t2s_attn_kernel's NT note)
-    unsigned dbg_skip = 0;         // GSV_BSTEP_SKIP (tuning aid): bit i drops launch K(i+1) of the batched chain -- timing only
     std::map<int, T2SBound> bound;
     // scratch sized for the largest bound batch
     int scratch_b = 0;
@@ -411,31 +411,46 @@ void t2s_launch_attn(gsv_t2s* h, const gsv_t2s_state& s, int l, const float* xsr
         k.seen = s.seen; k.step = s.step; k.eos_at = s.eos_at; k.emb = h->emb_audio; k.pe = h->pe_audio; k.eos_host = eos_host_of(s);
         k.V = h->cfg.vocab; k.eos = h->cfg.eos; k.n_pos = h->cfg.n_pos;
     }
+    // MODE of the kernel, chosen once for every shape below: layer 0 takes its input from the pending token (2) or from xsrc (0), a
+    // later layer from the previous layer's FFN partials (1)
+    auto with_mode = [&](auto launch) {
+        if (l == 0 && fused_token) launch(std::integral_constant<int, 2>{});
+        else if (l == 0) launch(std::integral_constant<int, 0>{});
+        else launch(std::integral_constant<int, 1>{});
+    };
     if (B > 16) {   // two sequences per block: one round of 1024-thread blocks up to 32 sequences (t2s_decode_multi.h)
         const size_t ml = sizeof(float) * attn_multi_lds_floats<2>();
-        if (l == 0 && fused_token) hipLaunchKernelGGL((t2s_attn_multi_kernel<WT, 2, 2>), dim3(kH, cdiv(B, 2)), dim3(kNT), ml, st, a, B);
-        else if (l == 0) hipLaunchKernelGGL((t2s_attn_multi_kernel<WT, 0, 2>), dim3(kH, cdiv(B, 2)), dim3(kNT), ml, st, a, B);
-        else hipLaunchKernelGGL((t2s_attn_multi_kernel<WT, 1, 2>), dim3(kH, cdiv(B, 2)), dim3(kNT), ml, st, a, B);
+        with_mode([&](auto mode) { hipLaunchKernelGGL((t2s_attn_multi_kernel<WT, decltype(mode)::value, 2>), dim3(kH, cdiv(B, 2)), dim3(kNT), ml, st, a, B); });
         return;
     }
+    // one sequence per block.  Only MODE 1 sums FFN partials (NJ of them) and has non-temporal weights (NT): layer 0 is <kNJ, false>
+    auto single = [&](auto nj, auto nt, auto ntkv) {
+        with_mode([&](auto mode) {
+            constexpr int MODE = decltype(mode)::value;
+            constexpr int NJ = MODE == 1 ? decltype(nj)::value : kNJ;
+            constexpr bool NT = MODE == 1 && decltype(nt)::value;
+            hipLaunchKernelGGL((t2s_attn_kernel<WT, MODE, NJ, NT, decltype(ntkv)::value>), dim3(kH, B), dim3(kNT), lds, st, a);
+        });
+    };
+    using Coarse = std::integral_constant<int, kNJ>;
+    using Fine = std::integral_constant<int, kNJFine>;
+    using NtF32 = std::bool_constant<sizeof(WT) == 4>;       // weights non-temporal: fp32 handles only
+    const bool fine = ffn_slices(B) == kNJFine;
     // K/V rows non-temporal from 4 sequences on: weights (152 MB) + a step's K/V rows (B x 49 KB x kv) then exceed what the Infinity
     // Cache holds (profiles/r03_kv_nontemporal.txt: at 1 sequence the hint costs 6 % at any kv -- everything fits; at 2 it pays only
     // beyond kv ~900; at 4 it is neutral at kv 250 and worth 3-5 % at kv 550-950; 0.354 -> 0.334 ms at 8, 0.411 -> 0.380 at 16).
     // GSV_SEQ_KV_NT_MIN_B moves the switch.
     static const int kvnt_b = getenv("GSV_SEQ_KV_NT_MIN_B") ? atoi(getenv("GSV_SEQ_KV_NT_MIN_B")) : 4;
     if (sizeof(WT) == 2 && B >= kvnt_b) {
-        if (l == 0 && fused_token) hipLaunchKernelGGL((t2s_attn_kernel<WT, 2, kNJ, false, true>), dim3(kH, B), dim3(kNT), lds, st, a);
-        else if (l == 0) hipLaunchKernelGGL((t2s_attn_kernel<WT, 0, kNJ, false, true>), dim3(kH, B), dim3(kNT), lds, st, a);
-        else if (ffn_slices<WT>(B) == kNJFine) hipLaunchKernelGGL((t2s_attn_kernel<WT, 1, kNJFine, false, true>), dim3(kH, B), dim3(kNT), lds, st, a);
-        else hipLaunchKernelGGL((t2s_attn_kernel<WT, 1, kNJ, false, true>), dim3(kH, B), dim3(kNT), lds, st, a);
+        if (fine) single(Fine{}, std::false_type{}, std::true_type{});
+        else single(Coarse{}, std::false_type{}, std::true_type{});
         return;
     }
-    if (l == 0 && fused_token) hipLaunchKernelGGL((t2s_attn_kernel<WT, 2>), dim3(kH, B), dim3(kNT), lds, st, a);
-    else if (l == 0) hipLaunchKernelGGL((t2s_attn_kernel<WT, 0>), dim3(kH, B), dim3(kNT), lds, st, a);
-    else if (ffn_slices<WT>(B) == kNJFine && sizeof(WT) == 4 && l >= h->nt_from_layer) hipLaunchKernelGGL((t2s_attn_kernel<WT, 1, kNJFine, sizeof(WT) == 4>), dim3(kH, B), dim3(kNT), lds, st, a);
-    else if (ffn_slices<WT>(B) == kNJFine) hipLaunchKernelGGL((t2s_attn_kernel<WT, 1, kNJFine>), dim3(kH, B), dim3(kNT), lds, st, a);
-    else if (sizeof(WT) == 4 && l >= h->nt_from_layer) hipLaunchKernelGGL((t2s_attn_kernel<WT, 1, kNJ, sizeof(WT) == 4>), dim3(kH, B), dim3(kNT), lds, st, a);
-    else hipLaunchKernelGGL((t2s_attn_kernel<WT, 1>), dim3(kH, B), dim3(kNT), lds, st, a);
+    const bool nt = sizeof(WT) == 4 && l >= h->nt_from_layer;
+    if (fine && nt) single(Fine{}, NtF32{}, std::false_type{});
+    else if (fine) single(Fine{}, std::false_type{}, std::false_type{});
+    else if (nt) single(Coarse{}, NtF32{}, std::false_type{});
+    else single(Coarse{}, std::false_type{}, std::false_type{});
 }
 
 template <typename WT>
@@ -446,20 +461,22 @@ void t2s_launch_ffn(gsv_t2s* h, const gsv_t2s_state& s, int l, hipStream_t st) {
     f.w1 = (const WT*)L.w1; f.b1 = L.b1; f.w2p = (const WT*)L.w2_p; f.zpart = (typename Geo<WT>::PT*)h->zpart; f.dbg = (l == h->cfg.n_layer - 1) ? h->dbg : nullptr;
     const int B = s.batch;
     static const int ffn_single_max_b = getenv("GSV_FFN_SINGLE_MAX_B") ? atoi(getenv("GSV_FFN_SINGLE_MAX_B")) : 8;   // tuning aid
-    bool four = false;
-#ifdef GSV_AB_KERNELS                   // four sequences per block (bf16 handles; spills 16 registers): an A/B kernel, not in the shipped library -- above 16
-    if constexpr (sizeof(WT) == 2) {     // sequences a bf16 handle runs the batched chain, and the per-sequence path behind it (caches beyond 1024 positions) R = 2
-        if (B > 16) { hipLaunchKernelGGL((t2s_ffn_multi_kernel<WT, 4>), dim3(kNJ, cdiv(B, 4)), dim3(kNT), sizeof(float) * ffn_multi_lds_floats<4>(), st, f, B); four = true; }
+    if (B > ffn_single_max_b) {
+        hipLaunchKernelGGL((t2s_ffn_multi_kernel<WT, 2>), dim3(kNJ, cdiv(B, 2)), dim3(kNT), sizeof(float) * ffn_multi_lds_floats<2>(), st, f, B);
+        return;
     }
-#endif
-    if (four) {}
-    else if (B > ffn_single_max_b) hipLaunchKernelGGL((t2s_ffn_multi_kernel<WT, 2>), dim3(kNJ, cdiv(B, 2)), dim3(kNT), sizeof(float) * ffn_multi_lds_floats<2>(), st, f, B);
-    else if (ffn_slices<WT>(B) == kNJFine) {
+    // one sequence per block; the weights non-temporal on the upper layers of an fp32 handle (t2s_attn_kernel's NT note)
+    auto single = [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        if (sizeof(WT) == 4 && l >= h->nt_from_layer) hipLaunchKernelGGL((t2s_ffn_kernel<WT, NJ, sizeof(WT) == 4>), dim3(NJ, B), dim3(kNT), 0, st, f);
+        else hipLaunchKernelGGL((t2s_ffn_kernel<WT, NJ>), dim3(NJ, B), dim3(kNT), 0, st, f);
+    };
+    if (ffn_slices(B) == kNJFine) {
         f.w2p = (const WT*)L.w2_p64;
-        if (sizeof(WT) == 4 && l >= h->nt_from_layer) hipLaunchKernelGGL((t2s_ffn_kernel<WT, kNJFine, sizeof(WT) == 4>), dim3(kNJFine, B), dim3(kNT), 0, st, f);
-        else hipLaunchKernelGGL((t2s_ffn_kernel<WT, kNJFine>), dim3(kNJFine, B), dim3(kNT), 0, st, f);
-    } else if (sizeof(WT) == 4 && l >= h->nt_from_layer) hipLaunchKernelGGL((t2s_ffn_kernel<WT, kNJ, sizeof(WT) == 4>), dim3(kNJ, B), dim3(kNT), 0, st, f);
-    else hipLaunchKernelGGL((t2s_ffn_kernel<WT>), dim3(kNJ, B), dim3(kNT), 0, st, f);
+        single(std::integral_constant<int, kNJFine>{});
+    } else {
+        single(std::integral_constant<int, kNJ>{});
+    }
 }
 
 // the R-sequences-per-block kernels use more than 64 KB of dynamic LDS
@@ -470,10 +487,6 @@ int t2s_multi_lds_attr() {
     HIPCHK(hipFuncSetAttribute((const void*)t2s_attn_multi_kernel<WT, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, la));
     HIPCHK(hipFuncSetAttribute((const void*)t2s_attn_multi_kernel<WT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, la));
     HIPCHK(hipFuncSetAttribute((const void*)t2s_ffn_multi_kernel<WT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ffn_multi_lds_floats<2>())));
-#ifdef GSV_AB_KERNELS
-    if constexpr (sizeof(WT) == 2)      // four sequences per block: bf16 handles only (t2s_launch_ffn); no fp32 instantiation exists
-        HIPCHK(hipFuncSetAttribute((const void*)t2s_ffn_multi_kernel<WT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ffn_multi_lds_floats<4>())));
-#endif
     return GSV_OK;
 }
 
@@ -499,7 +512,7 @@ int t2s_logits(gsv_t2s* h, const gsv_t2s_state& s, int mode, const float* hdirec
     a.tokpart = h->tokpart; a.kv_len = s.kv_len; a.bump = bump;
     if (staged) { a.step = staged->sg_step; a.logits = staged->sg_logits; a.hidden = staged->sg_hidden; a.tokpart = staged->sg_tok; a.kv_len = staged->sg_kv; }
     if (mode == 0) hipLaunchKernelGGL((t2s_logits_kernel<WT, 0>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
-    else if (ffn_slices<WT>(s.batch) == kNJFine) hipLaunchKernelGGL((t2s_logits_kernel<WT, 1, kNJFine>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
+    else if (ffn_slices(s.batch) == kNJFine) hipLaunchKernelGGL((t2s_logits_kernel<WT, 1, kNJFine>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
     else hipLaunchKernelGGL((t2s_logits_kernel<WT, 1>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
     HIPCHK(hipGetLastError());
     return GSV_OK;
@@ -544,18 +557,12 @@ struct ChainBufs {
 template <typename AttnFn>
 int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, AttnFn attn_launch, hipStream_t st, bool prompt = false) {
     const int rtiles = cdiv(M, 32);
-    const unsigned skip = h->dbg_skip;
     // A prompt pass re-reads its X tile once per 32-column tile at 32 x 32 output per block (9 056 rows: 870 MB per QKV
     // launch), so there a block walks 2 / 4 / 8 column tiles with its X rows -- and their LayerNorm -- in registers.  Measured
     // prompt pass, ms, blocks of 1 / 2 / 4 / 8 column tiles: 241 rows 1.18 / 1.13 / 1.41 / 2.00; 980 rows 2.00 / 1.60 / 1.64 /
     // 2.12; 1 968 rows 3.19 / 2.43 / 2.10 / 2.39; 4 000 rows 5.91 / 4.37 / 3.51 / 3.31; 9 056 rows 12.65 / - / - / 7.10.
     // The decode step (one row per sequence) keeps one tile per block: it lives on launch latency, not on bytes.
-    static const int force_cpb = getenv("GSV_CHAIN_CPB") ? atoi(getenv("GSV_CHAIN_CPB")) : 0;   // scan aid
-    int cpb = 1;
-    if (prompt) cpb = force_cpb > 0 ? force_cpb : (rtiles < 40 ? 2 : (rtiles < 100 ? 4 : 8));
-    // per launch (scan aid): GSV_CPB_K1 / K3 / K4 / K5 = column tiles per block of the QKV / out-proj / W1 / W2 launch of a prompt pass
-    static const int cpb_k[4] = {getenv("GSV_CPB_K1") ? atoi(getenv("GSV_CPB_K1")) : 0, getenv("GSV_CPB_K3") ? atoi(getenv("GSV_CPB_K3")) : 0,
-                                 getenv("GSV_CPB_K4") ? atoi(getenv("GSV_CPB_K4")) : 0, getenv("GSV_CPB_K5") ? atoi(getenv("GSV_CPB_K5")) : 0};
+    const int cpb = !prompt ? 1 : (rtiles < 40 ? 2 : (rtiles < 100 ? 4 : 8));
     auto run = [&](auto kern, int nthreads, BGemmArgs ba, int which = -1) {
         // per launch (profiles/r04_prompt_pass_cpb.txt): the out-proj and W2 launches have 16 column tiles only -- at up to ~20 row tiles (one or two
         // prompts) a tile per block (128 blocks pulling half the weights each) is 0.95 -> 0.88 ms per pass; QKV and W1 at 21-39 row tiles: four
@@ -563,18 +570,16 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
         if (prompt && which >= 0) {
             if (rtiles <= 20 && (which == 1 || which == 3)) cb = 1;
             if (rtiles > 20 && rtiles < 40 && (which == 0 || which == 2)) cb = 4;
-            if (cpb_k[which] > 0) cb = cpb_k[which];
         }
         ba.cpb = cb;
         hipLaunchKernelGGL(kern, dim3(rtiles, cdiv(ba.mtiles, cb)), dim3(nthreads), 0, st, ba);
     };
     // few rows (the decode step at 17 .. kSmallMaxM sequences, bf16 operands): 16 x 16 tiles, one wave per channel tile (t2s_small.h)
-    static const bool no_small = getenv("GSV_NO_SMALL_CHAIN") != nullptr;   // A/B switch
     static const int small_max = getenv("GSV_SMALL_MAX_M") ? atoi(getenv("GSV_SMALL_MAX_M")) : kSmallMaxM;   // tuning aid
     // NOT for a prompt pass, however few its rows (one 200-row prompt: TTFT 1.22 -> 0.98 ms on these kernels): the two tile shapes
     // sum k in different orders, and a request's K/V rows must not depend on how many prompts were packed into its pass
     // (tests/test_hip_t2s.py::test_prefill_into_scattered_slots_equals_one_by_one; the engine's ranks pack different sets)
-    const bool small = !prompt && !no_small && M <= small_max && h->layers[0].p16_qkv != nullptr && (!f8 || h->layers[0].p8_qkv != nullptr);
+    const bool small = !prompt && M <= small_max && h->layers[0].p16_qkv != nullptr && (!f8 || h->layers[0].p8_qkv != nullptr);
     const int rt16 = cdiv(M, 16);
     // (the prompt pass's weight fragments non-temporal, so that they do not evict the decode step's copy: measured, no gain in the
     // cb workload, TTFT 1.11 -> 1.37 ms: not adopted)
@@ -602,7 +607,7 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
     for (int l = 0; l < h->cfg.n_layer; ++l) {
         T2SLayer& L = h->layers[l];
         if (wide) {
-            if (!(skip & 1)) {   // K1
+            {   // K1
                 BGemmArgs g{};
                 g.M = M; g.ldx = kD; g.W = (const uint4*)L.g_qkv.w; g.mtiles = 3 * kD / 32; g.cout = 3 * kD; g.bias = L.g_qkv.bias; g.Y = c.qkv; g.ldy = 3 * kD;
                 if (l == 0) {
@@ -613,20 +618,20 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
                     if (int rc = run_wide(bgemm_wide_kernel<PRO_LN, float, bf16_t>, false, g)) return rc;
                 }
             }
-            if (!(skip & 2)) attn_launch(l);
-            if (!(skip & 4)) {   // K3
+            attn_launch(l);
+            {   // K3
                 BGemmArgs g{};
                 g.M = M; g.X = c.attn; g.ldx = kD; g.W = (const uint4*)L.g_out.w; g.mtiles = kD / 32; g.cout = kD; g.bias = L.bo;
                 g.res = x0; g.ldres = kD; g.Y = c.y1; g.ldy = kD;
                 if (int rc = run_wide(bgemm_wide_kernel<PRO_NONE, bf16_t, float>, false, g)) return rc;      // the attention's bf16 rows
             }
-            if (!(skip & 8)) {   // K4
+            {   // K4
                 BGemmArgs g{};
                 g.M = M; g.X = c.y1; g.ldx = kD; g.lng = L.ln1g; g.lnb = L.ln1b; g.xout = c.x1;
                 g.W = (const uint4*)L.g_w1.w; g.mtiles = kF / 32; g.cout = kF; g.bias = L.b1; g.relu = 1; g.Y = c.hid; g.ldy = kF;
                 if (int rc = run_wide(bgemm_wide_kernel<PRO_LN, float, bf16_t>, false, g)) return rc;
             }
-            if (!(skip & 16)) {  // K5
+            {  // K5
                 BGemmArgs g{};
                 g.M = M; g.X = c.hid; g.ldx = kF; g.W = (const uint4*)L.g_w2.w; g.mtiles = kD / 32; g.cout = kD;
                 g.bias = L.b2; g.res = c.x1; g.ldres = kD; g.Y = c.y2; g.ldy = kD;
@@ -635,7 +640,7 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
             continue;
         }
         if (small) {
-            if (!(skip & 1)) {   // K1
+            {   // K1
                 SGemmArgs g{};
                 g.M = M; g.W = (const uint4*)(f8 ? L.p8_qkv : L.p16_qkv); g.wscale = L.s_qkv; g.bias = L.g_qkv.bias; g.Y = c.qkv; g.ldy = 3 * kD;
                 const dim3 grid(rt16, 3 * kD / 32);
@@ -654,13 +659,13 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
                     else hipLaunchKernelGGL((sgemm_kernel<PRO_LN, float, 2>), grid, dim3(128), 0, st, g);
                 }
             }
-            if (!(skip & 2)) attn_launch(l);
-            if (!(skip & 4)) {   // K3 (bf16 on fp8 handles too)
+            attn_launch(l);
+            {   // K3 (bf16 on fp8 handles too)
                 SGemmArgs g{};
                 g.M = M; g.X = c.attn; g.W = (const uint4*)L.p16_out; g.bias = L.bo; g.res = x0; g.Y = c.y1; g.ldy = kD;
                 hipLaunchKernelGGL((sgemm_kernel<PRO_NONE, float, 2>), dim3(rt16, kD / 32), dim3(128), 0, st, g);
             }
-            if (!(skip & 8)) {   // K4
+            {   // K4
                 SGemmArgs g{};
                 g.M = M; g.X = c.y1; g.lng = L.ln1g; g.lnb = L.ln1b; g.xout = c.x1; g.W = (const uint4*)(f8 ? L.p8_w1 : L.p16_w1); g.wscale = L.s_w1;
                 g.bias = L.b1; g.relu = 1; g.Y = c.hid; g.ldy = kF;
@@ -669,7 +674,7 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
                 else if (nwv4) hipLaunchKernelGGL((sgemm_kernel<PRO_LN, bf16_t, 4>), dim3(rt16, kF / 64), dim3(256), 0, st, g);
                 else hipLaunchKernelGGL((sgemm_kernel<PRO_LN, bf16_t, 2>), dim3(rt16, kF / 32), dim3(128), 0, st, g);
             }
-            if (!(skip & 16)) {  // K5
+            {  // K5
                 SGemmArgs g{};
                 g.M = M; g.X = c.hid; g.W = (const uint4*)(f8 ? L.p8_w2 : L.p16_w2); g.wscale = L.s_w2; g.bias = L.b2; g.res = c.x1; g.Y = c.y2; g.ldy = kD;
                 if (f8) hipLaunchKernelGGL(sgemm_k_kernel<true>, dim3(rt16, kD / 16), dim3(256), 0, st, g);
@@ -677,7 +682,7 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
             }
             continue;
         }
-        if (!(skip & 1)) {   // K1: [LayerNorm2 of layer l-1] -> QKV
+        {   // K1: [LayerNorm2 of layer l-1] -> QKV
             BGemmArgs g{};
             g.M = M; g.ldx = kD; g.W = (const uint4*)(f8 ? L.f8_qkv : L.g_qkv.w); g.wscale = L.s_qkv; g.mtiles = 3 * kD / 32; g.cout = 3 * kD;
             g.bias = L.g_qkv.bias; g.Y = c.qkv; g.ldy = 3 * kD;
@@ -695,15 +700,15 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
                 else run(bgemm_kernel<PRO_LN, float, float, 4, false, true>, 256, g);
             }
         }
-        if (!(skip & 2)) attn_launch(l);
-        if (!(skip & 4)) {   // K3: out-proj + bias + residual -> pre-LN1
+        attn_launch(l);
+        {   // K3: out-proj + bias + residual -> pre-LN1
             BGemmArgs g{};
             g.M = M; g.X = c.attn; g.ldx = kD; g.W = (const uint4*)L.g_out.w; g.mtiles = kD / 32; g.cout = kD; g.bias = L.bo;
             g.res = x0; g.ldres = kD; g.Y = c.y1; g.ldy = kD;
             if (prompt) run(bgemm_kernel<PRO_NONE, bf16_t, float, 4, false>, 256, g, 1);
             else run(bgemm_kernel<PRO_NONE, float, float, 4, false, true>, 256, g);
         }
-        if (!(skip & 8)) {   // K4: [LayerNorm1] -> W1 + bias + ReLU
+        {   // K4: [LayerNorm1] -> W1 + bias + ReLU
             BGemmArgs g{};
             g.M = M; g.X = c.y1; g.ldx = kD; g.lng = L.ln1g; g.lnb = L.ln1b; g.xout = c.x1;
             g.W = (const uint4*)(f8 ? L.f8_w1 : L.g_w1.w); g.wscale = L.s_w1; g.mtiles = kF / 32; g.cout = kF; g.bias = L.b1; g.relu = 1;
@@ -711,7 +716,7 @@ int t2s_gemm_chain(gsv_t2s* h, int M, float* x0, const ChainBufs& c, bool f8, At
             if (f8) run(bgemm_kernel<PRO_LN, float, fp8_t, 4, true>, 256, g);
             else run(bgemm_kernel<PRO_LN, float, bf16_t, 4, false, true>, 256, g, 2);
         }
-        if (!(skip & 16)) {   // K5: W2 over the full K + bias + residual -> pre-LN2
+        {   // K5: W2 over the full K + bias + residual -> pre-LN2
             BGemmArgs g{};
             g.M = M; g.X = c.hid; g.ldx = kF; g.W = (const uint4*)(f8 ? L.f8_w2 : L.g_w2.w); g.wscale = L.s_w2; g.mtiles = kD / 32; g.cout = kD;
             g.bias = L.b2; g.res = c.x1; g.ldres = kD; g.Y = c.y2; g.ldy = kD;
@@ -740,22 +745,10 @@ int t2s_batched_layers(gsv_t2s* h, const gsv_t2s_state& s, hipStream_t st) {
         ba.qkv = c.qkv; ba.kc = (WT*)s.k_cache + (size_t)l * layer_elems; ba.vc = (WT*)s.v_cache + (size_t)l * layer_elems;
         ba.kv_len = s.kv_len; ba.T = T; ba.out = c.attn; ba.dbg = (l == h->cfg.n_layer - 1) ? h->dbg : nullptr;
         // K/V rows non-temporal: measured better at every batch size the chain serves (0.567 -> 0.517 ms per step at 32 sequences,
-        // 0.645 -> 0.595 at 64, 1.235 -> 1.168 at 256: profiles/r03_chain_small.txt); GSV_KV_NT_MIN_B moves the switch
-        static const int kv_nt_min_b = getenv("GSV_KV_NT_MIN_B") ? atoi(getenv("GSV_KV_NT_MIN_B")) : 0;
-        static const bool old_attn = getenv("GSV_OLD_BATTN") != nullptr;   // A/B switch: the first form (t2s_batch.h)
-        static const int dup = getenv("GSV_BATTN_DUP") ? atoi(getenv("GSV_BATTN_DUP")) : 0;   // timing aid: launch it 1 + dup times (the repeats read warm K/V)
-        for (int rep = 0; rep <= dup; ++rep)
-        if (old_attn) {
-            if (T <= 256) hipLaunchKernelGGL((t2s_batch_attn_kernel<4, false>), dim3(kH, B), dim3(256), 0, st, ba);
-            else if (T <= 512) hipLaunchKernelGGL((t2s_batch_attn_kernel<8, false>), dim3(kH, B), dim3(256), 0, st, ba);
-            else hipLaunchKernelGGL((t2s_batch_attn_kernel<16, false>), dim3(kH, B), dim3(256), 0, st, ba);
-        } else if (B >= kv_nt_min_b) {
-            if (T <= 256) hipLaunchKernelGGL((t2s_batch_attn2_kernel<4, true>), dim3(kH, B), dim3(256), 0, st, ba);
-            else if (T <= 512) hipLaunchKernelGGL((t2s_batch_attn2_kernel<8, true>), dim3(kH, B), dim3(256), 0, st, ba);
-            else hipLaunchKernelGGL((t2s_batch_attn2_kernel<16, true>), dim3(kH, B), dim3(256), 0, st, ba);
-        } else if (T <= 256) hipLaunchKernelGGL((t2s_batch_attn2_kernel<4>), dim3(kH, B), dim3(256), 0, st, ba);
-        else if (T <= 512) hipLaunchKernelGGL((t2s_batch_attn2_kernel<8>), dim3(kH, B), dim3(256), 0, st, ba);
-        else hipLaunchKernelGGL((t2s_batch_attn2_kernel<16>), dim3(kH, B), dim3(256), 0, st, ba);
+        // 0.645 -> 0.595 at 64, 1.235 -> 1.168 at 256: profiles/r03_chain_small.txt)
+        if (T <= 256) hipLaunchKernelGGL((t2s_batch_attn2_kernel<4, true>), dim3(kH, B), dim3(256), 0, st, ba);
+        else if (T <= 512) hipLaunchKernelGGL((t2s_batch_attn2_kernel<8, true>), dim3(kH, B), dim3(256), 0, st, ba);
+        else hipLaunchKernelGGL((t2s_batch_attn2_kernel<16, true>), dim3(kH, B), dim3(256), 0, st, ba);
     };
     // x0 = xcur: the token kernel rewrites it at the start of every step, so the chain may use it as its residual buffer
     if (int rc = t2s_gemm_chain(h, B, h->xcur, c, h->fp8, attn, st)) return rc;
@@ -1039,7 +1032,6 @@ int gsv_t2s_create(const gsv_t2s_config* cfg, gsv_t2s** out) {
     if (cfg->dtype == GSV_FP8) { h->fp8 = true; h->cfg.dtype = GSV_BF16; }   // bf16 everywhere but the batched step's QKV / FFN
     h->batched_min = kBatchedMinDefault;
     if (const char* e = getenv("GSV_BATCHED_MIN")) h->batched_min = std::max(1, atoi(e));
-    if (const char* e = getenv("GSV_BSTEP_SKIP")) h->dbg_skip = (unsigned)atoi(e);
     if (h->cfg.dtype == GSV_F32) h->nt_from_layer = kNtFromLayerF32;
     if (const char* e = getenv("GSV_NT_FROM_LAYER")) h->nt_from_layer = atoi(e);   // tuning aid
     if (getenv("GSV_NO_ARENA")) h->use_arena = false;
@@ -1412,7 +1404,7 @@ int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const
 }
 
 int gsv_t2s_batched_min(gsv_t2s* h) { return h && h->cfg.dtype == GSV_BF16 ? h->batched_min : 0x7fffffff; }
-int gsv_t2s_ffn_slices(gsv_t2s* h, int batch) { return !h ? kNJ : (h->cfg.dtype == GSV_F32 ? ffn_slices<float>(batch) : ffn_slices<bf16_t>(batch)); }
+int gsv_t2s_ffn_slices(gsv_t2s* h, int batch) { return !h ? kNJ : ffn_slices(batch); }
 
 size_t gsv_t2s_device_bytes(gsv_t2s* h) {
     if (!h) return 0;

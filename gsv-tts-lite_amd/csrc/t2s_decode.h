@@ -30,17 +30,16 @@ constexpr int kDh = 32;        // head dim
 constexpr int kF = 2048;       // MLP hidden
 constexpr int kNJ = 32;        // FFN slices (blocks) per sequence
 constexpr int kFJ = kF / kNJ;  // hidden units per slice
-// <= kFineMaxB sequences on a bf16 handle: 64 slices of 32 hidden units.  An FFN block then pulls 80 KB instead of 144 KB at the
+// <= kFineMaxB sequences: 64 slices of 32 hidden units.  On a bf16 handle an FFN block then pulls 80 KB instead of 144 KB at the
 // per-CU fabric rate, an attention block 32 KB more of (half) partial rows: -5 % on the step at 1-4 sequences, +3..10 % from 8 on
 // (profiles/r03_ffn_64_slices.txt), hence the switch.  The slice count is part of the arithmetic (each slice partial is rounded
 // to half): gsv_t2s_ffn_slices reports it and the oracle sums the same slices.
+// fp32 handles take the same switch (profiles/r05_step_f32_ffn64_ab.txt).  Their blocks pull twice the bytes (an FFN block 288 KB at
+// 32 slices, 144 KB at 64), and a launch costs ~2.5 us + bytes / 60 GB/s; the fp32 sum order is not the reference's either way (it
+// sums 2 048 products in one dot).
 constexpr int kNJFine = 64;
 constexpr int kFineMaxB = 4;
-// fp32 handles (round 5): the same switch.  Their blocks pull twice the bytes (an FFN block 288 KB at 32 slices, 144 KB at 64), and a
-// launch costs ~2.5 us + bytes / 60 GB/s; the fp32 sum order is not the reference's either way (it sums 2 048 products in one dot).
-// GSV_F32_FINE=0 keeps 32 slices (A/B).
-inline bool f32_fine() { static const bool on = !(getenv("GSV_F32_FINE") && atoi(getenv("GSV_F32_FINE")) == 0); return on; }
-template <typename WT> inline int ffn_slices(int B) { return (sizeof(WT) == 2 || f32_fine()) && B <= kFineMaxB ? kNJFine : kNJ; }
+inline int ffn_slices(int B) { return B <= kFineMaxB ? kNJFine : kNJ; }
 constexpr int kNP = 16;        // logits slices per sequence
 constexpr float kEps = 1e-5f;
 
@@ -151,49 +150,24 @@ __device__ __forceinline__ void lane_x(const float* xs, float (&xr)[8]) {
 }
 
 // ---- bf16 handles: dots on v_dot2c_f32_bf16 ---------------------------------------------------------------------------------
-// With the data in registers the attention / FFN blocks are VALU-issue bound (4 waves per SIMD; profiles/r03_decode_phase_stamps.txt:
-// 11k of the attention block's 17k cycles are arithmetic after its last load has landed), and half of a bf16 row dot's
-// instructions only unpack weights.  v_dot2c_f32_bf16 takes the packed weights as they were loaded and does two MACs per
-// instruction; its other operand must be bf16 too, so an activation enters as the PAIR hi + lo (hi = the value truncated to bf16,
-// lo = bf16(value - hi), which is exact before its rounding): 16 significant bits, a relative error <= 2^-17 per term -- far inside
-// the half rounding of the partial rows -- for one instruction per MAC and no unpack.  fp32 handles keep the fp32 FMA chain.
-// Round 5: the lo half is gone (kPairAct = false).  An activation enters a dot as ONE bf16 value, rounded to nearest -- what the
-// reference's own bf16 path multiplies (its activations ARE bf16 tensors), half the dot instructions of every GEMV of the step
-// (the kernels are vector-issue bound: profiles/r04_pmc_decode_b1_wave_cycles.txt), no lo arrays in LDS.  The bf16-mode oracle rounds
-// the same operands (ORC_R_LIN in the decode step: the input rows of QKV / out-proj / W1 / W2 and the query of the score dots).
-#ifndef GSV_PAIR_ACT
-#define GSV_PAIR_ACT 0      // 1: the (hi, lo) pair of rounds 3-4, an A/B build only (the bf16-mode oracle describes 0)
-#endif
-constexpr bool kPairAct = GSV_PAIR_ACT != 0;
+// With the data in registers the attention / FFN blocks are vector-issue bound (4 waves per SIMD: profiles/r03_decode_phase_stamps.txt,
+// profiles/r04_pmc_decode_b1_wave_cycles.txt), and half of an unpacked bf16 row dot's instructions only unpack weights.
+// v_dot2c_f32_bf16 takes the packed weights as they were loaded and does two MACs per instruction; its other operand must be bf16
+// too.  The rule: an activation enters a dot as ONE bf16 value, rounded to nearest (f32_to_bf16 at the store into LDS) -- what the
+// reference's own bf16 path multiplies (its activations ARE bf16 tensors), and what the bf16-mode oracle rounds (ORC_R_LIN in the
+// decode step: the input rows of QKV / out-proj / W1 / W2 and the query of the score dots; profiles/r05_step_hi_only_ab.txt).
+// A lane's eight activations are one raw16 read from that bf16 array.  fp32 handles keep the fp32 FMA chain.
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float dot2c(uint32_t w, uint32_t x, float acc) {
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, w), __builtin_bit_cast(bf16x2_t, x), acc, false);
 }
-// value -> (hi, lo) bf16 bit patterns
-__device__ __forceinline__ void split_bf16(float v, uint16_t& hi, uint16_t& lo) {
-    if constexpr (!kPairAct) { hi = f32_to_bf16(v); lo = 0; return; }
-    const uint32_t b = __float_as_uint(v);
-    hi = (uint16_t)(b >> 16);
-    lo = f32_to_bf16(v - __uint_as_float(b & 0xffff0000u));
-}
-// a lane's 8 activations (elements 8 lane .. 8 lane + 7 of a vector stored as two bf16 arrays) as packed pairs
-struct XPair { raw16 hi, lo; };
-__device__ __forceinline__ XPair xpair_load(const uint16_t* __restrict__ vh, const uint16_t* __restrict__ vl, int first) {
-    XPair x;
-    x.hi = *reinterpret_cast<const raw16*>(vh + first);
-    if constexpr (kPairAct) x.lo = *reinterpret_cast<const raw16*>(vl + first); else x.lo = raw16{};
-    return x;
-}
+// elements first .. first + 7 of a bf16 activation vector in LDS
+__device__ __forceinline__ raw16 x8_load(const uint16_t* __restrict__ v, int first) { return *reinterpret_cast<const raw16*>(v + first); }
 // 8 weights (one 16-byte load) . 8 activations
-__device__ __forceinline__ float dot8(const raw16& w, const XPair& x) {
-    float a = 0.f, b = 0.f;
-    if constexpr (!kPairAct) {     // two chains of two: a dependent dot2c issues every other slot
-        a = dot2c(w[0], x.hi[0], a); b = dot2c(w[1], x.hi[1], b);
-        a = dot2c(w[2], x.hi[2], a); b = dot2c(w[3], x.hi[3], b);
-        return a + b;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { a = dot2c(w[j], x.hi[j], a); b = dot2c(w[j], x.lo[j], b); }
+__device__ __forceinline__ float dot8(const raw16& w, const raw16& x) {
+    float a = 0.f, b = 0.f;     // two chains of two: a dependent dot2c issues every other slot
+    a = dot2c(w[0], x[0], a); b = dot2c(w[1], x[1], b);
+    a = dot2c(w[2], x[2], a); b = dot2c(w[3], x[3], b);
     return a + b;
 }
 // e^x of the softmax: fp32 handles keep expf (the parity mode); bf16 handles work in the base-2 domain on v_exp_f32
@@ -373,13 +347,13 @@ template <typename WT, int K> struct Panel {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) w[it] = ldg16w<NT>(panel + (size_t)(rsub + it * RPI) * K + part * EPL);
     }
-    // bf16 handles: the K-vector as bf16 hi / lo arrays (xpair_load)
+    // bf16 handles: the K-vector as a bf16 array in LDS
     template <typename OT>
-    __device__ __forceinline__ void finish2(const uint16_t* __restrict__ vh, const uint16_t* __restrict__ vl, OT* __restrict__ out) {
+    __device__ __forceinline__ void finish_bf16(const uint16_t* __restrict__ vec_lds, OT* __restrict__ out) {
         static_assert(EPL == 8, "bf16 panels");
         const int tid = threadIdx.x;
         const int part = tid % LPR, rsub = tid / LPR;
-        const XPair x = xpair_load(vh, vl, part * 8);
+        const raw16 x = x8_load(vec_lds, part * 8);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const float s = group_sum<LPR>(dot8(w[it], x));
@@ -505,27 +479,21 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     constexpr int EPL = Geo<WT>::EPL;
     constexpr int CPR = Geo<WT>::CPR;
     constexpr int LPR = kDh / EPL;         // lanes per K/V row
-#ifndef GSV_ATTN_WAVES
-#define GSV_ATTN_WAVES 8
-#endif
     // waves that run the attention phase (the others wait at its barrier).  The phase is VALU-issue bound and most of a wave's ~200 instructions
     // are per-wave overhead (running max / sum across the wave, the P.V reduction tree), not per-row work: eight waves with four K/V rows per
     // thread issue a quarter fewer instructions than sixteen with two (bf16: 0.2735 -> 0.2695 ms per step at one sequence, 0.297 -> 0.288 at 4;
     // fp32 handles keep sixteen: eight K/V vectors more per thread spill there, 0.433 -> 0.473 ms)
-    constexpr int AW = sizeof(WT) == 2 ? GSV_ATTN_WAVES : kNW;
+    constexpr int AW = sizeof(WT) == 2 ? 8 : kNW;
     constexpr int RPI = AW * 64 / LPR;     // K/V rows per block iteration (256 bf16, 128 f32 at 16 waves)
     constexpr int KCH = 2 * kNW / AW;      // iterations held in registers per chunk (512 positions bf16, 256 f32)
     const bool aw = __builtin_amdgcn_readfirstlane(wid) < AW;
     constexpr int RW = 96 / kNW;           // 6 QKV rows per wave
     const bool owner = tid < kD;
-    constexpr bool BF = sizeof(WT) == 2;   // bf16 handle: dots on v_dot2c_f32_bf16, activations as bf16 (hi, lo) pairs in LDS
-    uint16_t* xh = reinterpret_cast<uint16_t*>(xs);      // [512] hi, [512] lo over xs
-    uint16_t* xl = xh + kD;
-    uint16_t* qh = reinterpret_cast<uint16_t*>(qkv);     // q hi [32], q lo [32], the new key [32] over qkv[0..47]; v stays fp32 at qkv[64..]
-    uint16_t* ql = qh + 32;
+    constexpr bool BF = sizeof(WT) == 2;   // bf16 handle: dots on v_dot2c_f32_bf16, activations as bf16 in LDS (see dot8)
+    uint16_t* xh = reinterpret_cast<uint16_t*>(xs);      // [512] over xs
+    uint16_t* qh = reinterpret_cast<uint16_t*>(qkv);     // q [32] at qkv[0..15], the new key [32] at qkv[32..47]; v stays fp32 at qkv[64..]
     uint16_t* kn = qh + 64;
-    uint16_t* atth = reinterpret_cast<uint16_t*>(att);   // attention output hi [32], lo [32] over att
-    uint16_t* attl = atth + 32;
+    uint16_t* atth = reinterpret_cast<uint16_t*>(att);   // attention output [32] over att
     stamp(a.dbg, 0);
 
     // kv_len is loaded FIRST and used LAST: only the K/V row addresses need it.  (Clamping right here made hipcc wait for this --
@@ -586,10 +554,6 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     if constexpr (MODE == 0) asm volatile("" : "+v"(xd) : : "memory");
     else if constexpr (MODE == 2) asm volatile("" : "+v"(tl.tp.v) : : "memory");
     else asm volatile("" : "+v"(ps.p[0][0]) : : "memory");
-#ifdef GSV_DBG_DRAIN   // measurement only: every load of the block has landed before any arithmetic starts
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-    __syncthreads();
-#endif
     stamp(a.dbg, 1);
 
     // ---- layer input
@@ -604,7 +568,7 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
         v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
     }
     if (owner) {
-        if constexpr (BF) { uint16_t vh, vl; split_bf16(v, vh, vl); xh[tid] = vh; if constexpr (kPairAct) xl[tid] = vl; }
+        if constexpr (BF) xh[tid] = f32_to_bf16(v);
         else xs[tid] = v;
         if (h == 0) a.xout[(size_t)b * kD + tid] = v;
     }
@@ -616,7 +580,7 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     {
         float acc[8];
         if constexpr (BF) {
-            const XPair x = xpair_load(xh, xl, lane * 8);
+            const raw16 x = x8_load(xh, lane * 8);
 #pragma unroll
             for (int u = 0; u < 8; ++u) acc[u] = u < RW ? dot8(wq[u < RW ? u : 0][0], x) : 0.f;
         } else {
@@ -635,7 +599,7 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
                 if (row < 64) Kp[(size_t)nw * kDh + row - 32] = s; else Vp[(size_t)nw * kDh + row - 64] = s;
             }
             if constexpr (BF) {
-                if (row < 32) { uint16_t vh, vl; split_bf16(val, vh, vl); qh[row] = vh; if constexpr (kPairAct) ql[row] = vl; }
+                if (row < 32) qh[row] = f32_to_bf16(val);
                 else if (row < 64) kn[row - 32] = s;     // the new key is a bf16 value: it enters the score dot as it is
                 else qkv[row] = val;
             } else {
@@ -653,9 +617,9 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     // 1/sqrt(32); bf16 handles keep the scores in the base-2 domain (x log2 e) for v_exp_f32
     const float scale = BF ? 0.17677669529663687f * 1.4426950408889634f : 0.17677669529663687f;
     float qr[EPL];
-    XPair qp;
+    raw16 qp;
     if constexpr (BF) {
-        qp = xpair_load(qh, ql, part * 8);
+        qp = x8_load(qh, part * 8);
     } else {
 #pragma unroll
         for (int i = 0; i < EPL; ++i) qr[i] = qkv[part * EPL + i];
@@ -769,13 +733,13 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
         for (int w = 0; w < AW / 2; ++w) num = fmaf(pacc[(hf * (AW / 2) + w) * 32 + d], sm_exp<BF>(pm[hf * (AW / 2) + w] - M), num);
         num = xor32_sum(num);
         if (lane < 32) {
-            if constexpr (BF) { uint16_t vh, vl; split_bf16(num * __builtin_amdgcn_rcpf(den), vh, vl); atth[d] = vh; if constexpr (kPairAct) attl[d] = vl; }
+            if constexpr (BF) atth[d] = f32_to_bf16(num * __builtin_amdgcn_rcpf(den));
             else att[d] = num / den;
         }
     }
     __syncthreads();
     stamp(a.dbg, 5);
-    if constexpr (BF) po.finish2(atth, attl, a.ypart + ((size_t)b * kH + h) * kD);
+    if constexpr (BF) po.finish_bf16(atth, a.ypart + ((size_t)b * kH + h) * kD);
     else po.finish(att, a.ypart + ((size_t)b * kH + h) * kD);
     stamp(a.dbg, 6);
 }
@@ -810,10 +774,8 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     constexpr int RW = FJ / kNW;   // 4 (2) W1 rows per wave
     const bool owner = tid < kD;
     constexpr bool BF = sizeof(WT) == 2;   // bf16 handle: dots on v_dot2c_f32_bf16 (see dot8)
-    uint16_t* xh = reinterpret_cast<uint16_t*>(xs);
-    uint16_t* xl = xh + kD;
-    uint16_t* hbh = reinterpret_cast<uint16_t*>(hb);     // hidden units hi [FJ], lo [FJ] over hb
-    uint16_t* hbl = hbh + FJ;
+    uint16_t* xh = reinterpret_cast<uint16_t*>(xs);      // [512] over xs
+    uint16_t* hbh = reinterpret_cast<uint16_t*>(hb);     // hidden units [FJ] over hb
     stamp(a.dbg, 8);
 
     PartialSum<kH, typename Geo<WT>::PT> ps;
@@ -829,10 +791,6 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     const int oi = sumN_index<RW>();
     const float b1r = a.b1[row0 + oi];
     asm volatile("" : "+v"(ps.p[0][0]) : : "memory");
-#ifdef GSV_DBG_DRAIN
-    asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
-    __syncthreads();
-#endif
     stamp(a.dbg, 9);
 
     ps.park(stage);
@@ -842,7 +800,7 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     const float v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
     stamp(a.dbg, 15);
     if (owner) {
-        if constexpr (BF) { uint16_t vh, vl; split_bf16(v, vh, vl); xh[tid] = vh; if constexpr (kPairAct) xl[tid] = vl; }
+        if constexpr (BF) xh[tid] = f32_to_bf16(v);
         else xs[tid] = v;
         if (j == 0) a.x1out[(size_t)b * kD + tid] = v;
     }
@@ -851,7 +809,7 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     {
         float acc[RW];
         if constexpr (BF) {
-            const XPair x = xpair_load(xh, xl, lane * 8);
+            const raw16 x = x8_load(xh, lane * 8);
 #pragma unroll
             for (int u = 0; u < RW; ++u) acc[u] = dot8(w1r[u][0], x);
         } else {
@@ -863,13 +821,13 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
         const float tot = wave_sumN<RW>(acc);
         if ((lane & (64 / RW - 1)) == 0) {
             const float hv = fmaxf(tot + b1r, 0.f);
-            if constexpr (BF) { uint16_t vh, vl; split_bf16(hv, vh, vl); hbh[wid * RW + oi] = vh; if constexpr (kPairAct) hbl[wid * RW + oi] = vl; }
+            if constexpr (BF) hbh[wid * RW + oi] = f32_to_bf16(hv);
             else hb[wid * RW + oi] = hv;
         }
     }
     __syncthreads();
     stamp(a.dbg, 11);
-    if constexpr (BF) p2.finish2(hbh, hbl, a.zpart + ((size_t)b * NJ + j) * kD);
+    if constexpr (BF) p2.finish_bf16(hbh, a.zpart + ((size_t)b * NJ + j) * kD);
     else p2.finish(hb, a.zpart + ((size_t)b * NJ + j) * kD);
     stamp(a.dbg, 12);
 }

@@ -276,17 +276,18 @@ __global__ __launch_bounds__(256) void sgemm_k_kernel(SGemmArgs a) {
 }
 
 // ---- attention of the batched step, second form -------------------------------------------------------------------------------
-// t2s_batch_attn_kernel waits for kv_len before it issues any K/V load (the clamp needs it) and then computes all NIT x 64
-// positions of the bucket whatever kv_len is: 10.8 us per launch at 64 sequences with ~150 live positions (20 MB of K/V).  Here
+// The first form (kept in tools/battn_bench.hip as the A/B baseline) waited for kv_len before it issued any K/V load (the clamp needs
+// it) and then computed all NIT x 64 positions of the bucket whatever kv_len is: 10.8 us per launch at 64 sequences with ~150 live
+// positions (20 MB of K/V).  Here
 //   * the first two chunks (128 positions: a prompt alone is longer than that in most requests) are loaded BLIND at kernel entry,
 //     beside kv_len and the q / k / v row; when kv_len has landed the block continues in the straight-line body for its number of
 //     live chunks (2, 3, 4, 6, 8, 12 or 16 of 64 positions): the remaining loads of that body, clamped to the last live row;
 //   * a chunk with no live position costs no arithmetic (block-uniform branch), a live one half of it: scores on
-//     v_dot2c_f32_bf16 with q as a (hi, lo) bf16 pair (t2s_decode.h dot8), softmax in the base-2 domain on v_exp_f32.
+//     v_dot2c_f32_bf16 with q rounded to bf16 (t2s_decode.h dot8), softmax in the base-2 domain on v_exp_f32.
 // everything behind kv_len for a block with at most NCH live chunks of 64 positions (chunks 0 and 1 arrive loaded)
 template <int NCH, bool NTKV>
 __device__ __forceinline__ void battn2_rest(const BatchAttnArgs<bf16_t>& a, int h, int b, int n, int64_t n64, const raw16 (&kb)[2], const raw16 (&vb)[2],
-                                            float rq, float rk, float rv, uint16_t* qh, uint16_t* ql, uint16_t* knb, float* vn, float (*pacc)[32],
+                                            float rq, float rk, float rv, uint16_t* qh, uint16_t* knb, float* vn, float (*pacc)[32],
                                             float* pm, float* pl) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int part = tid & 3, rsub = tid >> 2;
@@ -305,9 +306,7 @@ __device__ __forceinline__ void battn2_rest(const BatchAttnArgs<bf16_t>& a, int 
     asm volatile("" : "+v"(rq), "+v"(rk), "+v"(rv) : : "memory");
     stamp(a.dbg, 2);
     if (tid < 32) {
-        uint16_t vh, vl;
-        split_bf16(rq, vh, vl);
-        qh[tid] = vh; if constexpr (kPairAct) ql[tid] = vl;
+        qh[tid] = f32_to_bf16(rq);
         const bf16_t kq = f32_to_bf16(rk), vq = f32_to_bf16(rv);
         knb[tid] = kq; vn[tid] = bf16_to_f32(vq);
         const int nw = n64 < 0 ? a.T - 1 : n;     // parked slot (kv_len < 0): away from the rows a staged refill writes
@@ -315,7 +314,7 @@ __device__ __forceinline__ void battn2_rest(const BatchAttnArgs<bf16_t>& a, int 
     }
     __syncthreads();
     stamp(a.dbg, 3);
-    const XPair qp = xpair_load(qh, ql, part * 8);
+    const raw16 qp = x8_load(qh, part * 8);
     const float scale = 0.17677669529663687f * 1.4426950408889634f;   // 1/sqrt(32) x log2 e
     float sc[NCH + 1];
     float mx = -INFINITY;
@@ -387,9 +386,9 @@ __device__ __forceinline__ void battn2_rest(const BatchAttnArgs<bf16_t>& a, int 
 
 // NTKV: the K/V rows are loaded non-temporally (they are read once per step and, from a few dozen sequences on, are larger than
 // the Infinity Cache: without the hint they evict the step's weights, which every GEMM launch then fetches from HBM)
-template <int NIT, bool NTKV = false>
+template <int NIT, bool NTKV>
 __global__ __launch_bounds__(256) void t2s_batch_attn2_kernel(BatchAttnArgs<bf16_t> a) {
-    __shared__ __attribute__((aligned(16))) uint16_t qh[32], ql[32], knb[32];
+    __shared__ __attribute__((aligned(16))) uint16_t qh[32], knb[32];
     __shared__ __attribute__((aligned(16))) float vn[32], pacc[4][32];
     __shared__ float pm[4], pl[4];
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -417,7 +416,7 @@ __global__ __launch_bounds__(256) void t2s_batch_attn2_kernel(BatchAttnArgs<bf16
     // chunks behind per-chunk branches made hipcc drain the load counter in every branch (0.654 -> 0.729 ms per step).
     const int nch = __builtin_amdgcn_readfirstlane((n + 63) >> 6);
     stamp(a.dbg, 1);
-#define GSV_BATTN_REST(N) battn2_rest<N, NTKV>(a, h, b, n, n64, kb, vb, rq, rk, rv, qh, ql, knb, vn, pacc, pm, pl)
+#define GSV_BATTN_REST(N) battn2_rest<N, NTKV>(a, h, b, n, n64, kb, vb, rq, rk, rv, qh, knb, vn, pacc, pm, pl)
     if (nch <= 2) GSV_BATTN_REST(2);
     else if (nch <= 3) GSV_BATTN_REST(3);
     else if (NIT <= 4 || nch <= 4) GSV_BATTN_REST(4);

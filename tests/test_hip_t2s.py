@@ -382,7 +382,7 @@ def test_greedy_infer_stream_fp32_matches_reference_golden(golden_dir, dev, name
 
 
 def test_batched_step_bf16_mfma_path_margin_gated(dev):
-    """bf16 with >= 36 slots runs the batched step (rowgemm GEMM chain on B rows + t2s_batch_attn_kernel; weights
+    """bf16 with >= 36 slots runs the batched step (rowgemm GEMM chain on B rows + t2s_batch_attn2_kernel; weights
     streamed once per step).  43 ragged requests through 40 slots (three refills), greedy: tokens must equal the
     fp32 oracle's continuous-batching output up to the first step whose oracle top-1/top-2 margin is below the
     bf16 noise bound; completion order bookkeeping must be a permutation."""

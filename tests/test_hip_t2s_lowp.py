@@ -11,7 +11,7 @@ What that does and does not allow (measured on MI355X, and the reason for each b
   * greedy tokens must agree wherever the oracle's top-1 / top-2 logit gap exceeds TOKEN_MARGIN = 5e-2: the measured
     logit noise of those flips after 24 layers.  Rounds 3-4 (the decode step's activations entered its dots with 16
     significant bits): largest gap at an observed divergence 9.4e-3 bf16, 1.7e-2 fp8, gate 2e-2.  Round 5: an activation is ONE
-    bf16 operand (the reference's own bf16 path multiplies bf16 activations; csrc/t2s_decode.h kPairAct), i.e. four more
+    bf16 operand (the reference's own bf16 path multiplies bf16 activations; csrc/t2s_decode.h dot8), i.e. four more
     operand vectors per layer that a 1e-6 difference can flip by a bf16 ulp: the same weak step of the bench request (step 107)
     now shows a gap of 2.6e-2 in the oracle, hence 5e-2 -- still 7x tighter than the bf16-vs-fp32 gate of the fp32-referenced
     tests (0.35).
