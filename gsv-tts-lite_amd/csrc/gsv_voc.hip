@@ -8,6 +8,7 @@
 #include "rbfuse.h"
 #include "encp.h"
 #include "voc_kernels.h"
+#include "vocseg.h"
 
 // =============================================================================================
 // SoVITS flow + Generator
@@ -1115,17 +1116,11 @@ int gsv_voc_flow_dec_graph(gsv_voc* v, const float* z_p, const float* y_mask, co
     return GSV_OK;
 }
 
-// y[c][j] = linear resampling of x[c][:] to T_out points, torch's F.interpolate(mode="linear", align_corners=False):
-// src = (j + 0.5) * T_in / T_out - 0.5 clamped at 0, weights (1 - frac, frac), right neighbour clamped to T_in - 1
+// y[c][j] = linear resampling of x[c][:] to T_out points (vocseg.h: resample_linear_at)
 static __global__ __launch_bounds__(256) void resample_linear_kernel(const float* __restrict__ x, int C, int T_in, float* __restrict__ y, int T_out) {
     const int j = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
     if (j >= T_out) return;
-    const float scale = (float)T_in / (float)T_out;
-    float src = ((float)j + 0.5f) * scale - 0.5f;
-    if (src < 0.f) src = 0.f;
-    const int i0 = min((int)src, T_in - 1), i1 = min(i0 + 1, T_in - 1);
-    const float f = src - (float)i0;
-    y[(size_t)c * T_out + j] = (1.0f - f) * x[(size_t)c * T_in + i0] + f * x[(size_t)c * T_in + i1];
+    y[(size_t)c * T_out + j] = resample_linear_at(x + (size_t)c * T_in, T_in, T_out, j);
 }
 
 int gsv_voc_resample_linear(const float* x, int C, int T_in, float* y, int T_out, void* stream) {
@@ -1142,19 +1137,8 @@ int gsv_voc_resample_linear(const float* x, int C, int T_in, float* y, int T_out
 // =============================================================================================
 namespace {
 
-__device__ __forceinline__ uint32_t dec_lowbias32(uint32_t h) {
-    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-    return h;
-}
-// standard normal for element `i` of the stream `seed`: Box-Muller over two counter-based uniforms (lowbias32 of the element
-// index mixed with the seed halves) -- replayable, no generator state; oracle.device_normal restates it
-__device__ __forceinline__ float dec_normal(uint32_t seed_lo, uint32_t seed_hi, uint32_t i) {
-    const uint32_t a = dec_lowbias32(dec_lowbias32(i * 0x9E3779B1u ^ seed_lo) + seed_hi);
-    const uint32_t b = dec_lowbias32(dec_lowbias32(i * 0x85EBCA77u ^ seed_hi ^ 0x68E31DA4u) + seed_lo);
-    const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
+// the per-frame arithmetic of the three kernels below (dec_normal, dec_zp_at, dec_ge_frame_at) lives in vocseg.h, shared with
+// the segmented kernel of gsv_voc_decode_segments
 
 // streaming (models.py:209-215, applied to the projected statistics: proj is 1x1 affine, so it commutes): drop the first
 // `start` frames, cross-fade the first `ov` kept frames with the previous chunk's tail
@@ -1184,7 +1168,7 @@ __global__ void dec_zp_kernel(const float* __restrict__ stats, int C, int T, flo
     const size_t n = (size_t)C * T;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float v = stats[i];
-        if (noise_scale != 0.f) v += dec_normal(seed_lo, seed_hi, (uint32_t)i) * expf(stats[n + i]) * noise_scale;
+        if (noise_scale != 0.f) v = dec_zp_at(v, stats[n + i], noise_scale, seed_lo, seed_hi, (uint32_t)i);
         z[i] = v;
         if (i < (size_t)T) mask[i] = 1.0f;
     }
@@ -1193,11 +1177,9 @@ __global__ void dec_zp_kernel(const float* __restrict__ stats, int C, int T, flo
 // resampled length (models.py:402): frame j reads column min(floor(j * (2 Tg / T_out)), 2 Tg - 1) / 2
 __global__ void dec_ge_frames_kernel(const float* __restrict__ ge, int gin, int Tg, float* __restrict__ out, int T_out, int resized) {
     const size_t n = (size_t)gin * T_out;
-    const float scale = (float)(2 * Tg) / (float)T_out;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i / T_out), j = (int)(i % T_out);
-        const int f = resized ? min((int)floorf((float)j * scale), 2 * Tg - 1) : j;
-        out[i] = ge[(size_t)c * Tg + (f >> 1)];
+        out[i] = ge[(size_t)c * Tg + (dec_ge_frame_at(j, 2 * Tg, T_out, resized) >> 1)];
     }
 }
 
@@ -1296,6 +1278,61 @@ int voc_decode_impl(gsv_voc* v, const int64_t* codes, int n_codes, const int64_t
     return voc_run<AT>(v, 3, w.z_p, w.mask, w.ge_fr, T_out, Tgv, out, w.voc, w.voc_bytes, st);
 }
 
+// ---- the same call over utterances that each have their own speed, noise scale and seed (gsv_voc_decode_segments)
+// The table as the kernel takes it (running offsets); returns 0 for a table the call refuses, with the reason left for
+// gsv_last_error unless `quiet` (the workspace query only answers 0).  Runs before anything is launched.
+int seg_table(const gsv_voc_segment* segs, int n_segments, int n_codes, int Tg, VocSegs* sg, bool quiet) {
+    auto bad = [&](const char* fmt, auto... a) { if (!quiet) (void)fail(GSV_ERR_ARG, fmt, a...); return 0; };
+    if (!segs) return bad("decode_segments: null segment table");
+    if (n_segments < 1 || n_segments > GSV_VOC_MAX_SEGMENTS) return bad("decode_segments: %d segments, 1..%d are taken", n_segments, GSV_VOC_MAX_SEGMENTS);
+    if (n_codes < 1 || (Tg != 1 && Tg != n_codes)) return bad("decode_segments: Tg %d is neither 1 nor n_codes %d", Tg, n_codes);
+    long long tok = 0, frames = 0;
+    sg->n = n_segments;
+    for (int i = 0; i < n_segments; ++i) {
+        if (segs[i].n_codes < 1) return bad("decode_segments: segment %d has n_codes %d", i, segs[i].n_codes);
+        if (segs[i].out_frames < 1) return bad("decode_segments: segment %d has out_frames %d", i, segs[i].out_frames);
+        sg->in0[i] = (int)(2 * tok);
+        sg->out0[i] = (int)frames;
+        sg->noise_scale[i] = segs[i].noise_scale;
+        sg->seed_lo[i] = (uint32_t)(segs[i].seed & 0xffffffffu);
+        sg->seed_hi[i] = (uint32_t)(segs[i].seed >> 32);
+        tok += segs[i].n_codes;
+        frames += segs[i].out_frames;
+        if (tok > n_codes) return bad("decode_segments: segments 0..%d hold %lld codes, the call has n_codes %d", i, tok, n_codes);
+        if (frames > (1 << 28)) return bad("decode_segments: segments 0..%d hold %lld output frames", i, frames);
+    }
+    if (tok != n_codes) return bad("decode_segments: the %d segments hold %lld codes, the call has n_codes %d", n_segments, tok, n_codes);
+    for (int i = n_segments; i <= VOC_MAX_SEGMENTS; ++i) { sg->in0[i] = (int)(2 * tok); sg->out0[i] = (int)frames; }
+    for (int i = n_segments; i < VOC_MAX_SEGMENTS; ++i) { sg->noise_scale[i] = 0.f; sg->seed_lo[i] = sg->seed_hi[i] = 0; }
+    return 1;
+}
+
+template <typename AT>
+int voc_decode_segments_impl(gsv_voc* v, const int64_t* codes, int n_codes, const int64_t* text, int P, const float* ge, int Tg,
+                             const int64_t* slice, const VocSegs& sg, float* out, float* attn, void* ws, size_t ws_bytes, hipStream_t st) {
+    const gsv_voc_config& c = v->cfg;
+    const int C = c.inter_channels, gin = c.gin_channels, T = 2 * n_codes, T_out = sg.out0[sg.n];
+    EncP& E = v->enc;
+    if (!E.has_ge512 && gin != 512) return fail(GSV_ERR_STATE, "decode_segments: %d-channel ge and no ge_to512 tensors", gin);
+    DecWs w = dec_layout(v, n_codes, P, Tg, T, T_out, (char*)ws);     // the layout of gsv_voc_decode; stats_s / stats_r stay unused
+    if (ws_bytes < w.bytes) return fail(GSV_ERR_ARG, "decode_segments workspace %zu < %zu", ws_bytes, w.bytes);
+    // ---- ge_to512 and enc_p on the whole concatenation, as gsv_voc_decode runs them
+    hipLaunchKernelGGL((cf_to_cl_kernel<AT>), dim3(cdiv(Tg, 32), cdiv(gin, 32)), dim3(256), 0, st, ge, (AT*)w.ge_cl, gin, Tg, gin);
+    if (E.has_ge512) {
+        if (int rc = run_cond<AT>(E.ge512, w.ge_cl, gin, Tg, w.ge512, 512, st)) return rc;
+    } else {
+        hipLaunchKernelGGL((cf_to_cl_kernel<float>), dim3(cdiv(Tg, 32), cdiv(gin, 32)), dim3(256), 0, st, ge, w.ge512, gin, Tg, gin);
+    }
+    int rc = sizeof(AT) == 2 ? encp_run(v, codes, n_codes, text, P, w.ge512, Tg == 1 ? 1 : T, 1, slice, w.stats, w.stats + (size_t)C * T, attn, w.enc, w.enc_bytes, st)
+                             : encp_run_f32(v, codes, n_codes, text, P, w.ge512, Tg == 1 ? 1 : T, 1, slice, w.stats, w.stats + (size_t)C * T, attn, w.enc, w.enc_bytes, st);
+    if (rc) return rc;
+    // ---- per segment: resampling, noise, conditioning map -> z_p, mask, ge_fr in one launch (vocseg.h)
+    hipLaunchKernelGGL(dec_segments_kernel, dim3(cdiv(T_out, 256), C + (Tg == 1 ? 1 : gin)), dim3(256), 0, st, (const float*)w.stats, C, T, sg, ge, gin, Tg,
+                       w.z_p, w.mask, w.ge_fr, T_out);
+    HIPCHK(hipGetLastError());
+    return voc_run<AT>(v, 3, w.z_p, w.mask, w.ge_fr, T_out, Tg == 1 ? 1 : T_out, out, w.voc, w.voc_bytes, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1321,6 +1358,27 @@ int gsv_voc_decode(gsv_voc* v, const int64_t* codes, int n_codes, const int64_t*
                                          overlap_state, has_overlap, use_graph, out, attn, workspace, workspace_bytes, S(stream))
                : voc_decode_impl<float>(v, codes, n_codes, text, n_text, ge, Tg, slice_indices, noise_scale, seed, out_frames, valid_start, overlap_len,
                                         overlap_state, has_overlap, use_graph, out, attn, workspace, workspace_bytes, S(stream));
+}
+
+size_t gsv_voc_decode_segments_workspace(gsv_voc* v, int n_codes, int n_text, int Tg, const gsv_voc_segment* segments, int n_segments) {
+    if (!v || !v->finalized || !v->enc.ready || n_codes < 1 || n_text < 1) return 0;
+    VocSegs sg;
+    if (!seg_table(segments, n_segments, n_codes, Tg, &sg, true)) return 0;
+    return dec_layout(v, n_codes, n_text, Tg, 2 * n_codes, sg.out0[sg.n], nullptr).bytes;
+}
+
+int gsv_voc_decode_segments(gsv_voc* v, const int64_t* codes, int n_codes, const int64_t* text, int n_text, const float* ge, int Tg,
+                            const int64_t* slice_indices, const gsv_voc_segment* segments, int n_segments, float* out, float* attn,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!v || !v->finalized) return fail(GSV_ERR_STATE, "vocoder not finalized");
+    if (!v->enc.ready) return fail(GSV_ERR_STATE, "decode_segments() needs the enc_p / quantizer tensors");
+    if (!codes || !text || !ge || !out || !workspace) return fail(GSV_ERR_ARG, "null argument");
+    if (n_codes < 1 || n_text < 1) return fail(GSV_ERR_ARG, "decode_segments: bad lengths");
+    VocSegs sg;                              // validated in full before anything is launched
+    if (!seg_table(segments, n_segments, n_codes, Tg, &sg, false)) return GSV_ERR_ARG;
+    return v->cfg.dtype == GSV_BF16
+               ? voc_decode_segments_impl<bf16_t>(v, codes, n_codes, text, n_text, ge, Tg, slice_indices, sg, out, attn, workspace, workspace_bytes, S(stream))
+               : voc_decode_segments_impl<float>(v, codes, n_codes, text, n_text, ge, Tg, slice_indices, sg, out, attn, workspace, workspace_bytes, S(stream));
 }
 
 int gsv_voc_flow(gsv_voc* v, const float* z_p, const float* y_mask, const float* ge, int T, int Tg, float* z_out,

@@ -22,6 +22,7 @@ EXPORTS = [
     "gsv_t2s_decode", "gsv_t2s_flush", "gsv_t2s_time_kernels", "gsv_t2s_set_debug", "gsv_t2s_batched_min", "gsv_t2s_ffn_slices", "gsv_t2s_device_bytes",
     "gsv_voc_create", "gsv_voc_destroy", "gsv_voc_load_tensor", "gsv_voc_finalize", "gsv_voc_workspace",
     "gsv_voc_flow_dec", "gsv_voc_flow_dec_graph", "gsv_voc_resample_linear", "gsv_voc_flow", "gsv_voc_dec", "gsv_voc_has_enc_p", "gsv_voc_enc_workspace", "gsv_voc_enc_p", "gsv_voc_decode_workspace", "gsv_voc_decode",
+    "gsv_voc_decode_segments_workspace", "gsv_voc_decode_segments",
     "gsv_align_workspace", "gsv_align_viterbi", "gsv_sola_workspace", "gsv_sola",
     "gsv_ref_create", "gsv_ref_destroy", "gsv_ref_load_tensor", "gsv_ref_finalize", "gsv_ref_workspace",
     "gsv_ref_spectrogram", "gsv_ref_get_ge", "gsv_ref_extract_latent",
@@ -60,6 +61,15 @@ class VocConfig(ctypes.Structure):
                 ("upsample_rates", ctypes.c_int * 8), ("upsample_kernel_sizes", ctypes.c_int * 8),
                 ("n_resblock_kernels", ctypes.c_int), ("resblock_kernel_sizes", ctypes.c_int * 4),
                 ("resblock_dilations", ctypes.c_int * 4), ("n_flows", ctypes.c_int), ("dtype", ctypes.c_int)]
+
+
+VOC_MAX_SEGMENTS = 64   # GSV_VOC_MAX_SEGMENTS: utterances per gsv_voc_decode_segments call
+
+
+class VocSegment(ctypes.Structure):
+    """gsv_voc_segment: one utterance of gsv_voc_decode_segments (24 bytes)"""
+    _fields_ = [("n_codes", ctypes.c_int32), ("out_frames", ctypes.c_int32), ("noise_scale", ctypes.c_float),
+                ("seed", ctypes.c_uint64)]
 
 
 class RefConfig(ctypes.Structure):
@@ -148,6 +158,7 @@ def lib():
         "gsv_voc_has_enc_p": [vp],
         "gsv_voc_enc_p": [vp, vp, i, vp, i, vp, i, vp, vp, vp, vp, vp, sz, vp],
         "gsv_voc_decode": [vp, vp, i, vp, i, vp, i, vp, ctypes.c_float, ctypes.c_uint64, i, i, i, vp, i, i, vp, vp, vp, sz, vp],
+        "gsv_voc_decode_segments": [vp, vp, i, vp, i, vp, i, vp, ctypes.POINTER(VocSegment), i, vp, vp, vp, sz, vp],
         "gsv_align_viterbi": [vp, i, i, i, vp, vp, sz, vp],
         "gsv_sola": [vp, vp, i, i, i, vp, vp, vp, sz, vp],
         "gsv_ref_create": [ctypes.POINTER(RefConfig), ctypes.POINTER(vp)],
@@ -199,6 +210,8 @@ def lib():
     L.gsv_voc_enc_workspace.restype = sz
     L.gsv_voc_decode_workspace.argtypes = [vp, i, i, i, i, i]
     L.gsv_voc_decode_workspace.restype = sz
+    L.gsv_voc_decode_segments_workspace.argtypes = [vp, i, i, i, ctypes.POINTER(VocSegment), i]
+    L.gsv_voc_decode_segments_workspace.restype = sz
     L.gsv_ref_workspace.argtypes = [vp, i, i, i]
     L.gsv_ref_workspace.restype = sz
     L.gsv_hubert_workspace.argtypes = [vp, i]

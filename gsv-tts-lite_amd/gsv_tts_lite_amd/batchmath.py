@@ -27,3 +27,32 @@ def split_bounds(lengths, samples_per_frame: int, speed: float):
         out.append((int(pos), int(nxt)))
         pos = nxt
     return out
+
+
+def segment_frames(lengths, speeds):
+    """Per-utterance frame counts of a segmented vocoder batch (SynthesizerTrn.decode_segments): utterance i of l_i tokens
+    at speed_i becomes 2 l_i frames at speed 1 and int(2 l_i / speed_i) + 1 otherwise -- the count models.py:217 gives that
+    utterance decoded alone, in Python doubles -- and starts at the running sum of the counts before it.
+    Returns [(out_frames, first_frame)]; the sample range of utterance i is (first_frame * hop, (first_frame + out_frames) * hop),
+    integers throughout (no accumulated float, unlike split_bounds)."""
+    if len(lengths) != len(speeds):
+        raise ValueError("%d lengths for %d speeds" % (len(lengths), len(speeds)))
+    out, first = [], 0
+    for l, s in zip(lengths, speeds):
+        l = int(l)
+        if l < 1:
+            raise ValueError("an utterance of %d tokens" % l)
+        if not s > 0:
+            raise ValueError("speed %r: must be positive" % (s,))
+        frames = 2 * l if s == 1 else int(2 * l / s) + 1
+        out.append((frames, first))
+        first += frames
+    return out
+
+
+def per_text_values(name: str, value, n_texts: int, seg2orig):
+    """TTS.infer_batched's per-text speed / noise_scale: one value per SEGMENT (the segments cut from a text inherit its
+    value); a number is repeated, a sequence of another length than the texts raises ValueError."""
+    from .slot_sampling import per_request
+    vals = per_request(name, value, n_texts)
+    return [vals[int(t)] for t in seg2orig]

@@ -238,6 +238,28 @@ class _VocoderNative:
                                  N.current_stream_ptr(self.device)))
         return out, attn
 
+    def decode_segments(self, codes, text, ge, slice_indices, segments):
+        """gsv_voc_decode_segments: `segments` = [(n_codes, out_frames, noise_scale, seed)] in batch order, at most
+        N.VOC_MAX_SEGMENTS -> (audio [1, 1, sum(out_frames) * hop], attn [4, 2n, P])"""
+        L = N.lib()
+        n, P, Tg = int(codes.numel()), int(text.numel()), int(ge.shape[-1])
+        table = (N.VocSegment * max(1, len(segments)))()
+        for e, (l, frames, ns, seed) in zip(table, segments):
+            e.n_codes, e.out_frames, e.noise_scale, e.seed = int(l), int(frames), float(ns), int(seed) & (2 ** 64 - 1)
+        need = L.gsv_voc_decode_segments_workspace(self._h, n, P, Tg, table, len(segments))
+        if need == 0:
+            raise RuntimeError("gsv_voc_decode_segments_workspace failed (n_codes %d, n_text %d, Tg %d, segments %r)" % (n, P, Tg, segments))
+        if getattr(self, "_dws", None) is None or self._dws.numel() < need:
+            self._dws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._dws
+        T_out = sum(int(s[1]) for s in segments)
+        out = torch.empty(1, 1, T_out * self.samples_per_frame, dtype=torch.float32, device=self.device)
+        attn = torch.empty(4, 2 * n, P, dtype=torch.float32, device=self.device)
+        N.check(L.gsv_voc_decode_segments(self._h, codes.data_ptr(), n, text.data_ptr(), P, ge.data_ptr(), Tg,
+                                          0 if slice_indices is None else slice_indices.data_ptr(), table, len(segments),
+                                          out.data_ptr(), attn.data_ptr(), ws.data_ptr(), ws.numel(), N.current_stream_ptr(self.device)))
+        return out, attn
+
     def dec(self, z, ge):
         z, ge, T, Tg = self._prep(z, ge)
         out = torch.empty(1, 1, T * self.samples_per_frame, dtype=torch.float32, device=self.device)
@@ -379,3 +401,48 @@ class SynthesizerTrn:
         o, attn = self._voc.decode(codes, text, ge, sl, noise_scale, seed, T_out, start, ov, state, has, bucket)
         self.enc_p.mrte.cross_attention.attn = attn[None]
         return o, attn
+
+    @torch.inference_mode()
+    def decode_segments(self, codes, text, ge, lengths, speeds, noise_scales, slice_indices=None, generator=None):
+        """`decode` over a time-concatenated batch whose utterances each have their own speed and noise scale, one library
+        call (gsv_voc_decode_segments).  codes [1, 1, N], text [1, P], ge [1, gin, 1] or [1, gin, N] and slice_indices as for
+        `decode`; utterance i is the next lengths[i] tokens (sum(lengths) == N, at most 64 utterances).  It is resampled on
+        its own to 2 l_i frames at speed 1, int(2 l_i / speed_i) + 1 otherwise -- no frame blends two utterances -- and gets
+        its own noise stream: one 64-bit seed per utterance with noise_scales[i] != 0 is drawn from `generator` (torch's default
+        CPU generator without one) in batch order, so a single utterance draws what `decode` draws.
+        Returns (audio [1, 1, T_out * hop], attn [4, 2N, P] over INPUT frames, bounds): bounds[i] is the exact sample range
+        (first_frame_i * hop, (first_frame_i + frames_i) * hop) of utterance i."""
+        from .batchmath import segment_frames
+        if self.enc_p is None:
+            raise RuntimeError("decode_segments() needs the enc_p / quantizer tensors in the state dict")
+        if codes.dim() != 3 or codes.shape[0] != 1 or codes.shape[1] != 1:
+            raise ValueError("decode_segments() takes codes of shape [1, 1, N], as decode() does")
+        lengths = [int(l) for l in lengths]
+        speeds = [s.item() if hasattr(s, "item") else s for s in speeds]
+        noise_scales = [float(x) for x in noise_scales]
+        n = int(codes.shape[-1])
+        if not (len(lengths) == len(speeds) == len(noise_scales)):
+            raise ValueError("lengths, speeds and noise_scales have %d, %d and %d entries" % (len(lengths), len(speeds), len(noise_scales)))
+        if not 1 <= len(lengths) <= N.VOC_MAX_SEGMENTS:
+            raise ValueError("%d utterances: one call takes 1..%d" % (len(lengths), N.VOC_MAX_SEGMENTS))
+        if sum(lengths) != n:
+            raise ValueError("lengths sum to %d, codes has %d tokens" % (sum(lengths), n))
+        dev = self.device
+        codes = codes.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        text = text.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        ge = ge.to(device=dev, dtype=torch.float32).reshape(self.gin_channels, -1).contiguous()
+        if ge.shape[-1] not in (1, n):
+            raise ValueError("ge must have 1 column or one per token (%d), got %d" % (n, ge.shape[-1]))
+        sl = None if slice_indices is None else slice_indices.to(device=dev, dtype=torch.int64).contiguous()
+        frames = segment_frames(lengths, speeds)
+        gdev = torch.device("cpu") if generator is None else generator.device
+        table = []
+        for l, (f, _), ns in zip(lengths, frames, noise_scales):
+            seed = 0
+            if ns != 0:    # drawn as decode() draws its one seed; an utterance without noise draws nothing
+                seed = int(torch.empty((), dtype=torch.int64, device=gdev).random_(generator=generator).item()) & (2 ** 64 - 1)
+            table.append((l, f, ns, seed))
+        o, attn = self._voc.decode_segments(codes, text, ge, sl, table)
+        self.enc_p.mrte.cross_attention.attn = attn[None]
+        hop = self.samples_per_frame
+        return o, attn, [(first * hop, (first + f) * hop) for f, first in frames]

@@ -51,8 +51,9 @@ import numpy as np
 import torch
 
 from . import slot_sampling
+from ._native import VOC_MAX_SEGMENTS
 from . import subtitles as sub
-from .batchmath import balance_order, split_bounds
+from .batchmath import balance_order, per_text_values, split_bounds
 from .stream import ChunkSplicer
 from .loader import Gpt, Sovits, convert_to_safetensors, get_gpt_weights, get_sovits_weights
 
@@ -938,17 +939,31 @@ class TTS:
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
-        inherit its values); see Text2SemanticDecoder.infer_batched.  noise_scale and speed are per call."""
+        inherit its values); see Text2SemanticDecoder.infer_batched.
+
+        speed / noise_scale: a number for the call -- the reference's path: each vocoder batch is resampled as one signal
+        and cut with `split_bounds` -- or a sequence with one value per TEXT (a wrong length raises ValueError).  With a
+        sequence for either, every segment is resampled on its own to its text's speed and gets its own noise stream
+        (SynthesizerTrn.decode_segments: no frame blends two utterances), the clips are cut at exact frame boundaries, the
+        mute after a segment is cut_mute / speed of its text, and return_subtitles aligns each segment on its own block of
+        the attention with its own speed; the last entry of a segment ends where that segment's audio ends.  A vocoder
+        batch then holds at most 64 segments (sovits_batch_size is capped there)."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
+                segmented = slot_sampling.is_sequence(speed) or slot_sampling.is_sequence(noise_scale)
+                if segmented:   # one value per text: the lengths are checked before any device work
+                    speed = slot_sampling.per_request("speed", speed, len(texts))
+                    noise_scale = slot_sampling.per_request("noise_scale", noise_scale, len(texts))
+                    if not all(s > 0 for s in speed):
+                        raise ValueError("speed must be positive, got %r" % (speed,))
                 if any(self._contains_chinese(t) for t in texts):
                     self._ensure_bert_loaded()
                 texts = [t if self._check_pause(t) else t + "." for t in texts]
                 if not is_cut_text:
                     cut_minlen = 10000
-                cut_mute = cut_mute / speed
+                cut_mute = [cut_mute / s for s in speed] if segmented else cut_mute / speed
                 n = len(texts)
                 bc = lambda v, kinds: [v] * n if isinstance(v, kinds) else list(v)
                 spk_audio_paths = bc(spk_audio_paths, (str, dict))
@@ -971,6 +986,10 @@ class TTS:
                         seg2orig.append(i)
                 sampling = {k: slot_sampling.per_segment(k, v, n, seg2orig) for k, v in
                             (("top_k", top_k), ("top_p", top_p), ("temperature", temperature), ("seed", seed))}
+                if segmented:   # host lists, the same on every rank: nothing about them is exchanged
+                    seg_speed = per_text_values("speed", speed, n, seg2orig)
+                    seg_noise = per_text_values("noise_scale", noise_scale, n, seg2orig)
+                    sovits_batch_size = min(sovits_batch_size, VOC_MAX_SEGMENTS)
                 eng = self._engine(t2s)     # None in a single process
                 if eng is not None:         # reference-speaker tensors exist on rank 0 only: ONE broadcast per new key
                     self._sync_speakers(prompt_audio_paths, prompt_audio_texts, spk_audio_paths, sovits_model)
@@ -1020,6 +1039,30 @@ class TTS:
                     ends = torch.cumsum(plens, 0)
                     pairs = torch.stack([ends - plens, ends], dim=1)
                     slice_indices = torch.repeat_interleave(pairs, (ln * 2).to(dev), dim=0)
+                    if segmented:   # per-segment speed / noise: exact frame bounds, one alignment per segment
+                        sp = [seg_speed[o] for o in oi]
+                        audio, attn, bounds = vq.decode_segments(torch.cat(sem).unsqueeze(0).unsqueeze(0), ph_cat, ge_cat, ln.tolist(), sp,
+                                                                 [seg_noise[o] for o in oi], slice_indices=slice_indices)
+                        audio = audio[0, 0, :]
+                        peak = audio.abs().max()
+                        if peak > 1.0:
+                            audio = audio / peak
+                        row, prange = 0, pairs.tolist()
+                        for k, (o, (lo, hi)) in enumerate(zip(oi, bounds)):
+                            a = audio[lo:hi]
+                            h, t = self._find_head_threshold_offsets(a), self._find_tail_threshold_offsets(a)
+                            audios.append(a[h:-t].float())
+                            rows = 2 * int(ln[k])
+                            if return_subtitles:
+                                assign = sub.viterbi_monotonic(attn[:, row:row + rows, prange[k][0]:prange[k][1]])
+                                part = sub.get_subtitles(word2ph_all[o], assign, sp[k], sovits_hz=self.sovits_hz)
+                                self._close_subtitles(part, word2ph_all[o], None)
+                                part[-1]["end_s"] = max(part[-1]["end_s"], (hi - lo) / self.samplerate)   # the segment's own audio
+                                part[0]["start_s"] += h / self.samplerate
+                                part[-1]["end_s"] -= t / self.samplerate
+                                subs_out.append(sub.sub2text_index(part, norm_all[o], segs[o]))
+                            row += rows
+                        continue
                     audio, attn = vq.decode(torch.cat(sem).unsqueeze(0).unsqueeze(0), ph_cat, ge_cat, noise_scale=noise_scale,
                                             speed=speed, cuda_graph=False, slice_indices=slice_indices)
                     audio = audio[0, 0, :]
@@ -1077,11 +1120,12 @@ class TTS:
                         sc = cut_mute_scale_map["…"]
                     else:
                         sc = 1.0
-                    per_text[seg2orig[k]].append(np.zeros(int(cut_mute * sc * self.samplerate), dtype=a.dtype))
+                    mute = cut_mute[seg2orig[k]] if segmented else cut_mute
+                    per_text[seg2orig[k]].append(np.zeros(int(mute * sc * self.samplerate), dtype=a.dtype))
                     if return_subtitles:   # TTS.py:843-852: spans are per segment; shift them into the whole text
                         if seg2orig[k] != last_orig:
                             cur_text_l, last_orig = 0, seg2orig[k]
-                        ordered_subs[k][-1]["end_s"] += cut_mute * sc
+                        ordered_subs[k][-1]["end_s"] += mute * sc
                         sub.increment_subtitle_indices(ordered_subs[k], cur_text_l)
                         per_text_subs[seg2orig[k]].append(ordered_subs[k])
                         cur_text_l += len(segs[k])

@@ -331,6 +331,35 @@ int gsv_voc_decode(gsv_voc* h, const int64_t* codes, int n_codes, const int64_t*
                    float* overlap_state, int has_overlap, int use_graph, float* out, float* attn, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* gsv_voc_decode over a time-concatenated batch whose utterances each have their own speed, noise scale and seed.  The
+ * `n_segments` entries of `segments` (a HOST array, 1..GSV_VOC_MAX_SEGMENTS, read before the call returns) follow one another:
+ * segment i covers codes [sum_{k<i} n_codes_k, + n_codes_i) -- input frames twice that -- and output frames
+ * [sum_{k<i} out_frames_k, + out_frames_i); sum n_codes_i == n_codes.  out_frames_i is the caller's int(2 n_codes_i / speed_i) + 1
+ * (2 n_codes_i for speed 1: copied, not resampled), evaluated once as for gsv_voc_decode.
+ *   ge_to512 and enc_p run on the whole concatenation (codes, text, ge, Tg in {1, n_codes}, slice_indices: as gsv_voc_decode).
+ *   Then ONE kernel writes z_p, the mask and the per-frame conditioning of all T_out = sum out_frames_i frames: each segment's
+ *   [m_p | logs_p] is resampled on its own (F.interpolate(mode="linear") of its 2 n_codes_i frames, both taps clamped to the
+ *   segment: no output frame blends two utterances), its noise is N(seed_i, c * out_frames_i + j) * exp(logs_p) * noise_scale_i
+ *   -- what gsv_voc_decode draws for that utterance alone with that seed; noise_scale_i == 0 adds nothing -- and frame j of the
+ *   segment takes the conditioning of its token min(floor(j * 2 n_codes_i / out_frames_i), 2 n_codes_i - 1) / 2.  flow +
+ *   Generator then run over T_out frames.  No streaming, no hipGraph.
+ *   -> out fp32 [T_out * prod(upsample_rates)]: segment i is samples [o_i, o_i + out_frames_i) * prod(upsample_rates);
+ *      attn fp32 [4][2 n_codes][n_text] (INPUT frames) or NULL.  workspace: gsv_voc_decode_segments_workspace(...) bytes, device.
+ * The table is checked before anything is launched: GSV_ERR_ARG, and gsv_last_error names the first bad entry, for n_segments
+ * outside 1..GSV_VOC_MAX_SEGMENTS, n_codes_i < 1, out_frames_i < 1, sum n_codes_i != n_codes or Tg outside {1, n_codes}; the
+ * workspace query returns 0 for the same inputs.  One segment with gsv_voc_decode's arguments gives gsv_voc_decode's samples. */
+#define GSV_VOC_MAX_SEGMENTS 64
+typedef struct gsv_voc_segment {
+    int32_t n_codes;     /* tokens of this utterance */
+    int32_t out_frames;  /* frames after its speed change */
+    float noise_scale;
+    uint64_t seed;       /* of its noise stream */
+} gsv_voc_segment;
+size_t gsv_voc_decode_segments_workspace(gsv_voc* h, int n_codes, int n_text, int Tg, const gsv_voc_segment* segments, int n_segments);
+int gsv_voc_decode_segments(gsv_voc* h, const int64_t* codes, int n_codes, const int64_t* text, int n_text, const float* ge, int Tg,
+                            const int64_t* slice_indices, const gsv_voc_segment* segments, int n_segments, float* out, float* attn,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Subtitle alignment: monotonic Viterbi path of vocoder frames over phonemes -- replaces
  * TTS._viterbi_monotonic (gsv_tts/TTS.py:1744-1797), which TTS.infer / infer_stream / infer_batched call on
  * the `attn` returned by vq_model.decode (TTS.py:250, 445, 769).
