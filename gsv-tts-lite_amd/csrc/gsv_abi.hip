@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -511,9 +512,16 @@ int t2s_logits(gsv_t2s* h, const gsv_t2s_state& s, int mode, const float* hdirec
     a.step = s.step; a.ctl = s.ctl; a.fctl = s.fctl; a.seen = s.seen; a.logits = s.logits; a.hidden = s.hidden;
     a.tokpart = h->tokpart; a.kv_len = s.kv_len; a.bump = bump;
     if (staged) { a.step = staged->sg_step; a.logits = staged->sg_logits; a.hidden = staged->sg_hidden; a.tokpart = staged->sg_tok; a.kv_len = staged->sg_kv; }
-    if (mode == 0) hipLaunchKernelGGL((t2s_logits_kernel<WT, 0>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
-    else if (ffn_slices(s.batch) == kNJFine) hipLaunchKernelGGL((t2s_logits_kernel<WT, 1, kNJFine>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
-    else hipLaunchKernelGGL((t2s_logits_kernel<WT, 1>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
+    // with a per-slot table the penalty and the suppression of slot b are table[b]'s (prompt passes read the table of the state they run in)
+    a.tab = tab_of(s);
+    auto launch = [&](auto tab) {
+        constexpr bool TAB = decltype(tab)::value;
+        if (mode == 0) hipLaunchKernelGGL((t2s_logits_kernel<WT, 0, kNJ, TAB>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
+        else if (ffn_slices(s.batch) == kNJFine) hipLaunchKernelGGL((t2s_logits_kernel<WT, 1, kNJFine, TAB>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
+        else hipLaunchKernelGGL((t2s_logits_kernel<WT, 1, kNJ, TAB>), dim3(kNP, nrows), dim3(kNT), 0, st, a);
+    };
+    if (a.tab) launch(std::true_type{});
+    else launch(std::false_type{});
     HIPCHK(hipGetLastError());
     return GSV_OK;
 }
@@ -880,6 +888,7 @@ struct AdoptArgs {
     int Bs, Ts, Bd, Td, esz;
     const int64_t *sg_kv, *sg_x; const int32_t *sg_step, *sg_eos; const float *sg_logits, *sg_hidden; const TokPart* sg_tok;
     int64_t *kv_len, *x_len, *tok_override; int32_t *step, *eos_at, *eos_host; float *logits, *hidden; TokPart* tokpart;
+    const unsigned char* s_seen; unsigned char* d_seen;   // the penalty set the pass penalised its first sample against: the steps go on with it
     int V;
 };
 __global__ __launch_bounds__(256) void t2s_adopt_kv_kernel(AdoptArgs a) {
@@ -899,7 +908,7 @@ __global__ __launch_bounds__(256) void t2s_adopt_kv_kernel(AdoptArgs a) {
 }
 __global__ __launch_bounds__(256) void t2s_adopt_state_kernel(AdoptArgs a) {
     const int ss = a.src[blockIdx.x], s = a.dst[blockIdx.x], tid = threadIdx.x;
-    for (int v = tid; v < a.V; v += 256) a.logits[(size_t)s * a.V + v] = a.sg_logits[(size_t)ss * a.V + v];
+    for (int v = tid; v < a.V; v += 256) { a.logits[(size_t)s * a.V + v] = a.sg_logits[(size_t)ss * a.V + v]; a.d_seen[(size_t)s * a.V + v] = a.s_seen[(size_t)ss * a.V + v]; }
     for (int c = tid; c < kD; c += 256) a.hidden[(size_t)s * kD + c] = a.sg_hidden[(size_t)ss * kD + c];
     if (tid < kNP) a.tokpart[(size_t)s * kNP + tid] = a.sg_tok[(size_t)ss * kNP + tid];
     if (tid == 0) {
@@ -963,6 +972,26 @@ struct PutSamplingArgs {
 __global__ __launch_bounds__(64) void t2s_put_sampling_kernel(PutSamplingArgs a) {
     const int r = blockIdx.x, tid = threadIdx.x;
     if (tid < kSlotSamplingWords) a.tab[kSlotSamplingWords * a.slot[r] + tid] = a.e[r][tid];
+}
+
+// The repetition-penalty set of slots that take a request (gsv_t2s_seed_seen): row r's slot is cleared, then marked with the
+// row's prompt tokens.  One block per row; the slot list and the row offsets ride in the kernel arguments.
+struct SeedSeenArgs {
+    short slot[kAdoptMax];
+    int off[kAdoptMax + 1];           // row r's tokens: tokens[off[r] .. off[r + 1])
+    const int64_t* tokens;
+    unsigned char* seen;              // [B][V]
+    int V;
+};
+__global__ __launch_bounds__(256) void t2s_seed_seen_kernel(SeedSeenArgs a) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    unsigned char* row = a.seen + (size_t)a.slot[r] * a.V;
+    for (int v = tid; v < a.V; v += 256) row[v] = 0;
+    __syncthreads();                  // the block's clears are ordered before its marks (same row, same block)
+    for (int i = a.off[r] + tid; i < a.off[r + 1]; i += 256) {
+        const int64_t t = a.tokens[i];
+        if (t >= 0 && t < a.V) row[t] = 1;
+    }
 }
 
 }  // namespace
@@ -1252,6 +1281,7 @@ int gsv_t2s_adopt_slots(gsv_t2s* h, int batch_dst, const int32_t* slots_dst, int
     a.sg_kv = sb->sg_kv; a.sg_x = sb->sg_x; a.sg_step = sb->sg_step; a.sg_eos = sb->sg_eos; a.sg_logits = sb->sg_logits; a.sg_hidden = sb->sg_hidden; a.sg_tok = sb->sg_tok;
     a.kv_len = d->st.kv_len; a.x_len = d->st.x_len; a.tok_override = d->st.tok_override; a.step = d->st.step; a.eos_at = d->st.eos_at; a.eos_host = d->st.eos_host;
     a.logits = d->st.logits; a.hidden = d->st.hidden; a.tokpart = h->tokpart; a.V = h->cfg.vocab;
+    a.s_seen = (const unsigned char*)sb->st.seen; a.d_seen = (unsigned char*)d->st.seen;
     for (int r0 = 0; r0 < nrows; r0 += kAdoptMax) {
         const int n = std::min(kAdoptMax, nrows - r0);
         for (int i = 0; i < n; ++i) { a.dst[i] = (short)slots_dst[r0 + i]; a.src[i] = (short)slots_src[r0 + i]; a.ovr[i] = tok_override ? (long long)tok_override[r0 + i] : -1; }
@@ -1391,6 +1421,10 @@ int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const
         if (slots[i] < 0 || slots[i] >= batch) return fail(GSV_ERR_ARG, "put_slot_sampling: slot %d out of range", (int)slots[i]);
         if (entries[i].sample_mode != 0 && entries[i].sample_mode != 2)
             return fail(GSV_ERR_ARG, "put_slot_sampling: entry %d has sample_mode %d (0 = greedy, 2 = device sampling)", i, (int)entries[i].sample_mode);
+        if (!std::isfinite(entries[i].rep_penalty) || entries[i].rep_penalty < 0.f)
+            return fail(GSV_ERR_ARG, "put_slot_sampling: entry %d has rep_penalty %g (0 = off, else a finite number > 0)", i, (double)entries[i].rep_penalty);
+        if (entries[i].suppress_steps < 0)
+            return fail(GSV_ERR_ARG, "put_slot_sampling: entry %d has suppress_steps %d (>= 0)", i, (int)entries[i].suppress_steps);
     }
     PutSamplingArgs a;
     a.tab = b->st.tab;
@@ -1399,6 +1433,27 @@ int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const
         for (int i = 0; i < n; ++i) { a.slot[i] = (short)slots[r0 + i]; memcpy(a.e[i], &entries[r0 + i], sizeof(gsv_t2s_slot_sampling)); }
         hipLaunchKernelGGL(t2s_put_sampling_kernel, dim3(n), dim3(64), 0, S(stream), a);
     }
+    HIPCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int gsv_t2s_seed_seen(gsv_t2s* h, int batch, const int32_t* slots, const int64_t* tokens, const int32_t* offsets, int nrows, void* stream) {
+    if (!h || !h->finalized) return fail(GSV_ERR_STATE, "handle not finalized");
+    T2SBound* b = t2s_find(h, batch);
+    if (!b) return fail(GSV_ERR_STATE, "no state bound for batch %d", batch);
+    if (!slots || !offsets || nrows < 1 || nrows > kAdoptMax || nrows > batch)
+        return fail(GSV_ERR_ARG, "seed_seen: need 1..min(batch, %d) rows, their slots and offsets (host arrays)", kAdoptMax);
+    for (int i = 0; i < nrows; ++i) {
+        if (slots[i] < 0 || slots[i] >= batch) return fail(GSV_ERR_ARG, "seed_seen: slot %d out of range", (int)slots[i]);
+        for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(GSV_ERR_ARG, "seed_seen: slot %d listed twice", (int)slots[i]);
+        if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return fail(GSV_ERR_ARG, "seed_seen: offsets must start at >= 0 and not decrease (row %d)", i);
+    }
+    if (offsets[nrows] > offsets[0] && !tokens) return fail(GSV_ERR_ARG, "seed_seen: %d tokens listed and no token array", (int)(offsets[nrows] - offsets[0]));
+    SeedSeenArgs a;
+    a.tokens = tokens; a.seen = (unsigned char*)b->st.seen; a.V = h->cfg.vocab;
+    for (int i = 0; i < nrows; ++i) { a.slot[i] = (short)slots[i]; a.off[i] = offsets[i]; }
+    a.off[nrows] = offsets[nrows];
+    hipLaunchKernelGGL(t2s_seed_seen_kernel, dim3(nrows), dim3(256), 0, S(stream), a);
     HIPCHK(hipGetLastError());
     return GSV_OK;
 }

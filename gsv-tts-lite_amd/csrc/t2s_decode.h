@@ -834,6 +834,11 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
 
 // ---- logits kernel -------------------------------------------------------------------------
 
+// One entry of the per-slot sampling table as the kernels read it: {sample_mode, top_k, temperature, top_p} (token kernel) and
+// {seed_lo, seed_hi, rep_penalty, suppress_steps} (seeds: token kernel; penalty and suppression: logits kernel)
+// (gsv_t2s_slot_sampling, include/gsv_tts_hip.h).
+constexpr int kSlotSamplingWords = 2;
+
 template <typename WT>
 struct LogitsArgs {
     // final hidden: MODE 1 -> LN2(sum zpart + b2 + x1) of the last layer; MODE 0 -> hdirect[B][512]
@@ -857,9 +862,17 @@ struct LogitsArgs {
     TokPart* tokpart;    // [B][kNP]
     int64_t* kv_len;     // bumped by slice 0 when bump != 0
     int bump;
+    // TAB: the per-slot sampling table (gsv_t2s_set_slot_sampling); its second word carries slot b's penalty and suppression.  LAST, so that
+    // the kernel arguments the table-less instantiation reads stay where they were (the same code, instruction for instruction)
+    const u32x4* tab;
 };
 
-template <typename WT, int MODE, int NJ = kNJ>
+// TAB: slot b's repetition penalty, suppress_steps and first-sample suppression come from the second word of its table entry
+// ({seed_lo, seed_hi, rep_penalty, suppress_steps}) instead of fctl[0] / ctl[1] / ctl[7] / ctl[2]: requests with and without the
+// anti-loop rules of `infer` then sit side by side in one launch.  A penalty of 0 or 1.0 leaves the slot's logits untouched (no
+// scaling at all: bit-identical to the scalar call's), suppress_steps 0 suppresses nothing.  Without a table the kernel is the
+// <false> instantiation, which reads ctl / fctl only.
+template <typename WT, int MODE, int NJ = kNJ, bool TAB = false>
 __global__ __launch_bounds__(kNT) void t2s_logits_kernel(LogitsArgs<WT> a) {
     __shared__ __attribute__((aligned(16))) float smem[kD + 2 * kNW + 128 + kNW * kD];
     float* xs = smem;
@@ -877,8 +890,16 @@ __global__ __launch_bounds__(kNT) void t2s_logits_kernel(LogitsArgs<WT> a) {
 
     // the control words are loaded FIRST and used LAST (as scalars): loaded behind the weight rows, their first use drained the
     // whole load counter before the LayerNorm could start
-    int c_step = a.step[b], c_sup = a.ctl[1], c_first = a.ctl[7], c_rep = a.ctl[2];
-    float c_rp = a.fctl[0];
+    int c_step = a.step[b], c_sup, c_first, c_rep;
+    float c_rp;
+    if constexpr (TAB) {
+        // one 16-byte load whose address depends on nothing but the slot; the flags are derived when the words are used
+        const u32x4 e1 = a.tab[kSlotSamplingWords * b + 1];
+        c_rp = __uint_as_float(e1[2]); c_sup = (int)e1[3]; c_first = 0; c_rep = 0;
+    } else {
+        c_sup = a.ctl[1]; c_first = a.ctl[7]; c_rep = a.ctl[2];
+        c_rp = a.fctl[0];
+    }
     PartialSum<NJ, typename Geo<WT>::PT> ps;
     float xd = 0.f;
     if constexpr (MODE == 0) {
@@ -900,8 +921,9 @@ __global__ __launch_bounds__(kNT) void t2s_logits_kernel(LogitsArgs<WT> a) {
     const int myr = wid * rww + oi;             // slice row this lane will emit (if oi < rww)
     const uint8_t sn = a.seen[(size_t)b * a.V + min(vbase + myr, a.V - 1)];
     asm volatile("" : "+v"(c_step), "+v"(c_sup), "+v"(c_first), "+v"(c_rep), "+v"(c_rp) : : "memory");
-    const bool sup = c_step < c_sup || (a.vlimit < a.V && c_first != 0);
-    const bool rep = c_rep != 0;
+    // TAB: the first sample is suppressed iff the request suppresses at all; a penalty of 0 (an entry never written) or 1.0 is off
+    const bool sup = c_step < c_sup || (a.vlimit < a.V && (TAB ? c_sup > 0 : c_first != 0));
+    const bool rep = TAB ? (c_rp != 0.f && c_rp != 1.0f) : c_rep != 0;
     const float rp = c_rp;
     if constexpr (MODE == 0) asm volatile("" : "+v"(xd) : : "memory");
     else asm volatile("" : "+v"(ps.p[0][0]) : : "memory");
@@ -975,10 +997,6 @@ struct TokenArgs {
     int32_t* eos_host;       // null, or a host-mapped mirror of eos_at
     const u32x4* tab;        // null, or the per-slot sampling table (gsv_t2s_set_slot_sampling): two 16-byte words per slot
 };
-
-// One entry of the per-slot sampling table as the token kernel reads it: {sample_mode, top_k, temperature, top_p} and
-// {seed_lo, seed_hi, -, -} (gsv_t2s_slot_sampling, include/gsv_tts_hip.h).
-constexpr int kSlotSamplingWords = 2;
 
 // Counter-based uniform in (0, 1): one draw per (seed, slot, absolute position, vocabulary entry).  The
 // reference draws Exp(1) noise from torch's generator (GPT/utils.py:56-59); a device sampler cannot share

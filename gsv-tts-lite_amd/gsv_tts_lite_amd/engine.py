@@ -180,8 +180,8 @@ class ContinuousBatchingEngine:
 
     def run_gpt(self, xs, ys, berts, costs: Optional[Sequence[float]] = None, **sampling):
         """-> (pred, idx): this rank's finished requests, completion order, GLOBAL indices.  `sampling` goes to
-        `infer_batched` as it is: per-request top_k / top_p / temperature / seed lists are indexed by the GLOBAL request
-        index and every rank holds the same lists (they are arguments of the collective call), so nothing crosses ranks."""
+        `infer_batched` as it is: per-request top_k / top_p / temperature / seed / repetition_penalty /
+        initial_suppression_steps lists are indexed by the GLOBAL request index and every rank holds the same lists (they are arguments of the collective call), so nothing crosses ranks."""
         if costs is None:
             costs = [int(x.shape[0]) for x in xs]
         src = self._source(costs)

@@ -4,12 +4,15 @@
 `Text2SemanticDecoder.infer_batched` takes top_k / top_p / temperature / seed as scalars (one set per call, as the
 reference, t2s_model.py:555-734) or as sequences indexed like its requests.  This module turns them into one entry per
 request -- {sample_mode, top_k, temperature, top_p, seed, noise stream} -- and does nothing else: no torch, no device.
+
+The anti-loop rules of `infer` (t2s_model.py:415-416, 444-447) ride in the same entry: `repetition_penalty` as a SEQUENCE
+(a number is ignored by the batched loop, as in the reference, :637-651) and `initial_suppression_steps` (0: none).
 """
 from __future__ import annotations
 
 from numbers import Integral, Real
 
-_ARGS = ("top_k", "top_p", "temperature", "seed")
+_ARGS = ("top_k", "top_p", "temperature", "seed", "repetition_penalty", "initial_suppression_steps")
 
 
 def is_sequence(v) -> bool:
@@ -51,10 +54,24 @@ def split_seed(seed: int):
     return int(seed) & 0x7fffffff, (int(seed) >> 31) & 0x7fffffff
 
 
+class Entry(tuple):
+    """one request's table entry: the six sampling words (sample_mode, top_k, temperature, top_p, seed_lo, seed_hi) as the tuple
+    itself, and the two anti-loop words beside them as `rep_penalty` / `suppress_steps`; `words()` is all eight in the order
+    of gsv_t2s_slot_sampling"""
+
+    def __new__(cls, sampling, rep_penalty, suppress_steps):
+        e = super().__new__(cls, sampling)
+        e.rep_penalty, e.suppress_steps = float(rep_penalty), int(suppress_steps)
+        return e
+
+    def words(self):
+        return tuple(self) + (self.rep_penalty, self.suppress_steps)
+
+
 class RequestSampling:
     """one entry per request; `begin` fixes the call's seed, `entry(i)` is what goes into the slot that takes request i"""
 
-    def __init__(self, n, top_k, top_p, temperature, seed):
+    def __init__(self, n, top_k, top_p, temperature, seed, repetition_penalty=None, initial_suppression_steps=0):
         ks = per_request("top_k", top_k, n)
         ps = per_request("top_p", top_p, n)
         ts = per_request("temperature", temperature, n)
@@ -69,10 +86,30 @@ class RequestSampling:
         # top_k == 1 is the argmax: greedy for that request, as _sampling_mode decides for a whole call
         self.mode = [0 if k == 1 else 2 for k in self.top_k]
         self.call_seed = 0
+        # a NUMBER for repetition_penalty is the reference's batched behaviour: ignored (t2s_model.py:637-651); None: 1.0
+        rs = per_request("repetition_penalty", repetition_penalty, n) if is_sequence(repetition_penalty) else [None] * n
+        self.rep_penalty = [1.0 if v is None else float(v)
+                            for v in (_number("repetition_penalty", i, v, Real, True) for i, v in enumerate(rs))]
+        for i, v in enumerate(self.rep_penalty):
+            if not (0.0 < v < float("inf")):
+                raise ValueError("repetition_penalty[%d] is %r: expected a finite number > 0" % (i, v))
+        ns = per_request("initial_suppression_steps", initial_suppression_steps, n)
+        self.suppress_steps = [int(_number("initial_suppression_steps", i, v, Integral)) for i, v in enumerate(ns)]
+        for i, v in enumerate(self.suppress_steps):
+            if v < 0:
+                raise ValueError("initial_suppression_steps[%d] is %r: expected an integer >= 0" % (i, v))
 
     @property
     def any_sampled(self) -> bool:
         return any(m == 2 for m in self.mode)
+
+    @property
+    def any_penalised(self) -> bool:
+        """ctl[2] of the call: the steps keep `seen` up to date iff a request penalises"""
+        return any(r != 1.0 for r in self.rep_penalty)
+
+    def penalised(self, i: int) -> bool:
+        return self.rep_penalty[i] != 1.0
 
     def begin(self, draw_seed):
         """(ctl[0], the call's seed): the seed is drawn ONCE, and only if a request samples -- what a scalar call does, so a
@@ -88,13 +125,24 @@ class RequestSampling:
         return i + 1 if self.seed[i] is None else 1
 
     def entry(self, i: int):
-        """(sample_mode, top_k, temperature, top_p, seed_lo, seed_hi) of request i"""
+        """(sample_mode, top_k, temperature, top_p, seed_lo, seed_hi) of request i, with .rep_penalty / .suppress_steps (`Entry`);
+        a penalty of 1.0 goes into the table as 0: off, the slot's logits are not scaled at all"""
         lo, hi = split_seed(self.call_seed if self.seed[i] is None else self.seed[i])
-        return self.mode[i], self.top_k[i], self.temperature[i], self.top_p[i], lo, hi
+        return Entry((self.mode[i], self.top_k[i], self.temperature[i], self.top_p[i], lo, hi),
+                     self.rep_penalty[i] if self.penalised(i) else 0.0, self.suppress_steps[i])
 
 
-def resolve(n: int, top_k, top_p, temperature, seed=None):
-    """None when the call has one set of parameters (all scalars, no seed): no table is bound and the call is the scalar one"""
-    if seed is None and not any(is_sequence(v) for v in (top_k, top_p, temperature)):
+def _nonzero_steps(v) -> bool:
+    """anything but the scalar integer 0: a sequence, a count, or a value whose type the table's validation will name"""
+    if hasattr(v, "item") and not is_sequence(v):
+        v = v.item()            # a 0-d array / tensor is a scalar
+    return not (isinstance(v, Integral) and not isinstance(v, bool) and v == 0)
+
+
+def resolve(n: int, top_k, top_p, temperature, seed=None, repetition_penalty=None, initial_suppression_steps=0):
+    """None when the call has one set of parameters (all scalars, no seed, a scalar repetition_penalty -- which the batched loop
+    ignores -- and no suppression): no table is bound and the call is the scalar one"""
+    if (seed is None and not any(is_sequence(v) for v in (top_k, top_p, temperature, repetition_penalty))
+            and not _nonzero_steps(initial_suppression_steps)):
         return None
-    return RequestSampling(n, top_k, top_p, temperature, seed)
+    return RequestSampling(n, top_k, top_p, temperature, seed, repetition_penalty, initial_suppression_steps)

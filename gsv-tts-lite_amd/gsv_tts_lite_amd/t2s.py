@@ -452,8 +452,38 @@ class Text2SemanticDecoder:
             return
         n = len(slots)
         sl = (ctypes.c_int32 * n)(*[int(v) for v in slots])
-        en = (N.SlotSampling * n)(*[N.SlotSampling(*samp.entry(int(c))) for c in requests])
+        en = (N.SlotSampling * n)(*[N.SlotSampling(*samp.entry(int(c)).words()) for c in requests])
         N.check(N.lib().gsv_t2s_put_slot_sampling(self._h, batch, sl, en, n, N.current_stream_ptr(self.device)))
+
+    def _seed_tokens(self, requests, y):
+        """the prompt tokens of the penalising requests among `requests`, packed on the device by the current stream, and the
+        row offsets (gsv_t2s_seed_seen); None when the call keeps no penalty sets"""
+        samp = self._samp
+        if samp is None or not samp.any_penalised or not len(requests):
+            return None
+        off, rows = [0], []
+        for c in requests:          # a request that does not penalise gets an empty row: its slot's set is only cleared
+            if samp.penalised(int(c)):
+                rows.append(y[int(c)].reshape(-1))
+            off.append(off[-1] + (int(rows[-1].numel()) if samp.penalised(int(c)) else 0))
+        tok = torch.cat(rows).to(device=self.device, dtype=torch.int64) if rows else None
+        return tok, off
+
+    def _put_request(self, batch, slots, requests, seed):
+        """the slots of state `batch` take these requests: their penalty sets (cleared; the prompt tokens of a request that
+        penalises) and their table entries, on the current stream -- BEFORE the prompt pass, whose logits obey both"""
+        if self._samp is None or not len(slots):
+            return
+        slots = [int(v) for v in slots]
+        if seed is not None:
+            tok, off = seed
+            for r0 in range(0, len(slots), 64):         # the slot list rides in the kernel arguments: 64 rows per launch
+                n = min(64, len(slots) - r0)
+                sl = (ctypes.c_int32 * n)(*slots[r0: r0 + n])
+                of = (ctypes.c_int32 * (n + 1))(*off[r0: r0 + n + 1])
+                N.check(N.lib().gsv_t2s_seed_seen(self._h, batch, sl, None if tok is None else tok.data_ptr(), of, n,
+                                                  N.current_stream_ptr(self.device)))
+        self._put_sampling(batch, slots, requests)
 
     def _stream_id(self, c):
         """tok_override of a slot that takes request c under device sampling: its noise stream + 1"""
@@ -708,7 +738,11 @@ class Text2SemanticDecoder:
                 xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in rq], [y[c] for c in rq], [bert_feature[c] for c in rq])
                 sl = torch.tensor([i for i, _, _ in group], dtype=torch.int32, device=dev)
                 ids = torch.tensor([self._stream_id(c) for _, c, _ in group], dtype=torch.int64, device=dev)
+                seed = self._seed_tokens(rq, y)
                 side.wait_event(ev)
+                # the parked slots' penalty sets and table entries, behind the last step that recorded their previous tenants' tokens:
+                # the steps leave a parked slot's `seen` alone, and what they read of its entry goes nowhere
+                self._put_request(B, [i for i, _, _ in group], rq, seed)
                 self.prefill_slots_staged(B, sl, xy1, xl1, yl1, side.cuda_stream)
                 done = torch.cuda.Event()
                 done.record(side)
@@ -736,7 +770,6 @@ class Text2SemanticDecoder:
             if stream_by_request:       # device sampling: the joined slots draw from their requests' noise streams
                 rt["tok_override"].index_copy_(0, sl.long(), _keep[3])
                 _keep[3].record_stream(main)
-            self._put_sampling(B, [i for i, _, _ in group], [c for _, c, _ in group])
             for i, _, n_new in group:
                 state[i], steps[i], start[i], joined[i] = LIVE, 0, n_new, window
             inflight.clear()
@@ -824,9 +857,10 @@ class Text2SemanticDecoder:
         tails = [t for t in (self._tail_state(lv, cap) for lv in sorted(set(self.tail_levels), reverse=True) if lv < B) if t is not None]
         B0 = B
         if self._samp is not None:
-            # compaction carries a slot's entry to the tail state's table (gsv_t2s_move_slots).  The ahead state has none: it is
-            # never stepped, and an adopted request's first token is drawn by the token kernel of the adopting state
-            for t in tails:
+            # compaction carries a slot's entry to the tail state's table (gsv_t2s_move_slots).  The ahead state is never stepped,
+            # but its prompt passes penalise and suppress the first sample by ITS table and `seen`; the adopting state's token
+            # kernel draws that sample, so the entry goes into both (`top_up`, `fill`)
+            for t in tails + [sh]:
                 self._bind_sampling(t)
         for k in ("ctl", "fctl"):
             sh[k].copy_(rt[k])          # the prompt pass's first logits obey the same control words
@@ -931,8 +965,10 @@ class Text2SemanticDecoder:
             with torch.cuda.stream(side):
                 xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in rq], [y[c] for c in rq], [bert_feature[c] for c in rq])
                 sl = torch.tensor([i for i, _, _ in group], dtype=torch.int32, device=dev)
+                seed = self._seed_tokens(rq, y)
                 if adopted_ev[0] is not None:
                     side.wait_event(adopted_ev[0])
+                self._put_request(sh["batch"], [i for i, _, _ in group], rq, seed)
                 self.prefill_slots_staged(sh["batch"], sl, xy1, xl1, yl1, side.cuda_stream)
                 done = torch.cuda.Event()
                 done.record(side)
@@ -1054,7 +1090,7 @@ class Text2SemanticDecoder:
                       top_k: int = 15, top_p: float = 1.0, temperature: float = 1.0,
                       repetition_penalty: float = 1.35, check_interval: int = 5, generator=None,
                       source=None, slots: int = None, on_finish=None, max_new_tokens=None, async_refill: bool = False,
-                      seed=None):
+                      seed=None, initial_suppression_steps=0):
         """t2s_model.py:555-734: continuous batching over the slots of one batch-size family.
 
         `top_k`, `top_p`, `temperature` and `seed` are scalars -- one set for the call, as in the reference -- or sequences
@@ -1063,6 +1099,15 @@ class Text2SemanticDecoder:
         gsv_t2s_set_slot_sampling).  With `seed` None the noise is keyed as in a scalar call: one seed drawn from `generator`,
         stream = request index.  `seed[i]` given: request i draws from (seed[i], stream 0), so its tokens depend on its own
         inputs, parameters and seed only.  All scalars and no seed: no table is bound, the call is the scalar one.
+
+        `repetition_penalty` as a NUMBER is ignored, as in the reference's batched loop, which samples without the penalty
+        (t2s_model.py:637-651); the default stays for signature compatibility.  As a SEQUENCE indexed like the requests it is
+        applied: request i is penalised over its prompt's and its generated tokens as `infer` penalises (1.0: not at all) --
+        `repetition_penalty=[1.35] * len(x)` is `infer`'s rule for every request.  `initial_suppression_steps` (an int for the
+        call or a sequence per request; not in the reference's batched loop) is `infer`'s start rule: 0 suppresses nothing,
+        n > 0 bars 280 / 486 / EOS from the prefill's sample and from every sample while idx < n (t2s_model.py:415-416, 444-447).
+        Either one makes the call a table call.  With both, and top_k=1 in fp32, a request returns the tokens `infer` returns
+        for it, whichever slot it lands in and however it is refilled.
 
         `source` (engine.RequestSource) replaces "the next request is x[cur]" (:696-700) by "the next request is
         whatever the shared queue hands this rank": x / y / bert_feature are then the GLOBAL lists, the returned
@@ -1073,7 +1118,7 @@ class Text2SemanticDecoder:
         request i once it has produced that many tokens -- tested at the same 5-step cadence as EOS, cut exactly.
         `async_refill` (not in the reference, whose slots all wait while a refill's prompt pass runs, :696-722) runs the
         slot loop of `_infer_batched_staged` instead: same requests, same tokens per request, no stall."""
-        samp = SS.resolve(len(x), top_k, top_p, temperature, seed)
+        samp = SS.resolve(len(x), top_k, top_p, temperature, seed, repetition_penalty, initial_suppression_steps)
         if samp is None:
             return self._infer_batched_call(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval,
                                             generator, source, slots, on_finish, max_new_tokens, async_refill)
@@ -1142,7 +1187,9 @@ class Text2SemanticDecoder:
         if async_refill and self.refill_ahead > 0:
             # bound BEFORE the first prompt pass: binding a state may re-allocate the handle's per-slot scratch (pending tokens)
             self._ahead_state(max(1, min(self.refill_ahead, batch_size)), max(caps))
-        self._set_ctl(rt, mode, 0, False, 1.0, top_k, temperature, seed, top_p)
+        # a scalar repetition_penalty is ignored, as in the reference's batched loop (t2s_model.py:637-651).  Per request, penalty
+        # and suppression are table words; ctl[2] makes the steps keep `seen` up to date when any request penalises
+        self._set_ctl(rt, mode, 0, self._samp is not None and self._samp.any_penalised, 1.0, top_k, temperature, seed, top_p)
         if self._samp is not None:
             self._bind_sampling(rt)
         rt["kv_len"].zero_()
@@ -1157,12 +1204,12 @@ class Text2SemanticDecoder:
                 break
         if lmax > caps[-1]:
             raise ValueError("prompt longer than the largest KV bucket")
+        self._put_request(batch_size, range(actual), first, self._seed_tokens(first, y))
         self.prefill(batch_size, 0, xy, xl, yl)
         rows = torch.arange(batch_size, device=dev)
         if mode == 2:       # device sampling: the noise stream of a slot is its REQUEST (placement-invariant samples)
             rt["tok_override"].zero_()
             rt["tok_override"][:actual] = torch.tensor([self._stream_id(c) for c in first], dtype=torch.int64, device=dev)
-        self._put_sampling(batch_size, range(actual), first)
         if async_refill:
             try:
                 loop = self._infer_batched_ahead if self.refill_ahead > 0 else self._infer_batched_staged
@@ -1260,10 +1307,10 @@ class Text2SemanticDecoder:
                 # scattered slots (gsv_t2s_prefill_slots) instead of one 170-launch chain per sequence
                 req = [c for _, c in refill]
                 xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in req], [y[c] for c in req], [bert_feature[c] for c in req])
+                self._put_request(batch_size, [i for i, _ in refill], req, self._seed_tokens(req, y))
                 self.prefill_slots(batch_size, [i for i, _ in refill], xy1, xl1, yl1)
                 self.last_stats["refills"] += len(refill)
                 if mode == 2:
                     rt["tok_override"][torch.tensor([i for i, _ in refill], device=dev)] = \
                         torch.tensor([self._stream_id(c) for _, c in refill], dtype=torch.int64, device=dev)
-                self._put_sampling(batch_size, [i for i, _ in refill], req)
         return pred, torch.tensor(orig, device=dev)

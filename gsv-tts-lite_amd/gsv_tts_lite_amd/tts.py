@@ -937,9 +937,15 @@ class TTS:
                                           ",": 1.0, "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0,
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
-                      bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None):
+                      bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
+                      initial_suppression_steps=0):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
+
+        repetition_penalty: a NUMBER is ignored, as in the reference's batched loop; a sequence with one value per TEXT is
+        applied to that text's segments as `infer` applies it (`[1.35] * len(texts)` for every text).  initial_suppression_steps:
+        0 (none, the reference's batched behaviour), an int for the call, or one per TEXT: `infer`'s start rule for those
+        segments.  A sequence of the wrong length raises ValueError.
 
         speed / noise_scale: a number for the call -- the reference's path: each vocoder batch is resampled as one signal
         and cut with `split_bounds` -- or a sequence with one value per TEXT (a wrong length raises ValueError).  With a
@@ -985,7 +991,9 @@ class TTS:
                         segs.append(c)
                         seg2orig.append(i)
                 sampling = {k: slot_sampling.per_segment(k, v, n, seg2orig) for k, v in
-                            (("top_k", top_k), ("top_p", top_p), ("temperature", temperature), ("seed", seed))}
+                            (("top_k", top_k), ("top_p", top_p), ("temperature", temperature), ("seed", seed),
+                             ("repetition_penalty", repetition_penalty),
+                             ("initial_suppression_steps", initial_suppression_steps))}
                 if segmented:   # host lists, the same on every rank: nothing about them is exchanged
                     seg_speed = per_text_values("speed", speed, n, seg2orig)
                     seg_noise = per_text_values("noise_scale", noise_scale, n, seg2orig)
@@ -1009,14 +1017,13 @@ class TTS:
                 if eng is None:
                     # staged refill: same tokens per request as the reference-order loop (greedy: rows are independent;
                     # sampling: the noise stream is the request's), no stall of the other slots on a prompt pass
-                    pred, orig_idx = t2s.infer_batched(ids, prompts, berts, repetition_penalty=repetition_penalty,
-                                                       async_refill=True, **sampling)
+                    pred, orig_idx = t2s.infer_batched(ids, prompts, berts, async_refill=True, **sampling)
                     tokens = [None] * len(segs)
                     for p_, o in zip(pred, orig_idx.tolist()):
                         tokens[o] = p_
                 else:   # this rank's share of the segment queue (engine.py), then every rank learns every segment's tokens
                     pred, orig_idx = eng.run_gpt(ids, prompts, berts, costs=[int(i.shape[0]) for i in ids],
-                                                 repetition_penalty=repetition_penalty, async_refill=True, **sampling)
+                                                 async_refill=True, **sampling)
                     tokens = eng.exchange({int(o): p_ for p_, o in zip(pred, orig_idx.tolist())}, len(segs), dst=None)
                     eng._retire_cursors(None)
                 # TTS.py:705-716 sorts the COMPLETION-order list by length; completion order depends on slot timing (and on

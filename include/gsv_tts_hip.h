@@ -112,29 +112,50 @@ int gsv_t2s_set_eos_mirror(gsv_t2s* h, int batch, int32_t* host_mapped);
 /* Optional: PER-SLOT sampling parameters for one bound state (continuous batching whose requests bring their own top_k / top_p /
  * temperature / seed; the reference's batched loop has one set per call, t2s_model.py:555-734).  `table` is a caller-owned DEVICE
  * array of `batch` entries, 16-byte aligned, or NULL to turn it off.  With a table the token step takes slot b's sample_mode
- * (0 greedy | 2 device sampling) and parameters from table[b] instead of ctl[0], ctl[4..6], fctl[1..2]; suppress_steps,
- * rep_enabled, suppress_first and the repetition penalty stay in ctl / fctl, and ctl[0] == 1 (host tokens) stays a whole-state
- * mode that overrides the table.  The entries are read from device memory by every step, so one captured step serves any mix and
- * an entry may change between two gsv_t2s_decode calls.  A slot's pending token is drawn by the token kernel of the NEXT step (or
- * gsv_t2s_flush) of the state the slot lives in, so a request's entry has to be in place there before that step, wherever its
- * prompt pass ran (gsv_t2s_prefill*, gsv_t2s_commit_slots, gsv_t2s_adopt_slots); gsv_t2s_move_slots carries a moved slot's entry
- * to the destination's table (GSV_ERR_ARG when the source has a table and the destination has none).  GSV_STEP_FUSED_TOKEN keeps
- * its meaning: the caller's promise that no slot samples.  Call after gsv_t2s_bind_state (which clears it); a change of the table
- * pointer invalidates the captured steps of this batch size. */
+ * (0 greedy | 2 device sampling) and parameters from table[b] instead of ctl[0], ctl[4..6], fctl[1..2], and the logits kernel --
+ * of every step AND of every prompt pass that runs in this state -- takes slot b's repetition penalty, suppress_steps and
+ * first-sample suppression from table[b] instead of fctl[0], ctl[1], ctl[7] (first-sample suppression is on iff suppress_steps
+ * > 0; the penalty is applied iff rep_penalty is neither 0 nor 1, whatever ctl[2] says).  What stays in ctl: ctl[0] == 1 (host
+ * tokens), a whole-state mode that overrides the table, and ctl[2], the whole-state switch "keep `seen` up to date": set it when
+ * any request that may run in the state penalises (the token step then records every live slot's tokens in its `seen` row).
+ * The entries are read from device memory by every step, so one captured step serves any mix and an entry may change between two
+ * gsv_t2s_decode calls.
+ * ORDER.  The prompt pass's logits are penalised and suppressed, so a request's entry AND its `seen` row (gsv_t2s_seed_seen) have
+ * to be in place in the state where its PROMPT PASS runs, before that pass: the stepped state for gsv_t2s_prefill /
+ * gsv_t2s_prefill_slots / gsv_t2s_prefill_slots_staged into a parked slot (the steps leave a parked slot's `seen` row alone), the
+ * ahead state's own table and `seen` for a pass that gsv_t2s_adopt_slots moves later.  The slot's pending token is drawn by the
+ * token kernel of the next step (or gsv_t2s_flush) of the state the slot lives in, so after gsv_t2s_adopt_slots (which carries
+ * the `seen` row, not the entry) the entry is put into the adopting state's table as well, before its next step.
+ * gsv_t2s_commit_slots needs nothing; gsv_t2s_move_slots carries a moved slot's entry and `seen` row to the destination
+ * (GSV_ERR_ARG when the source has a table and the destination has none).  GSV_STEP_FUSED_TOKEN keeps its meaning: the caller's
+ * promise that no slot samples.  Call after gsv_t2s_bind_state (which clears it); a change of the table pointer invalidates the
+ * captured steps of this batch size. */
 typedef struct {
     int32_t sample_mode;    /* 0 greedy argmax | 2 device sampling */
     int32_t top_k;          /* as ctl[4] */
     float temperature;      /* as fctl[1] */
     float top_p;            /* as fctl[2] */
     int32_t seed_lo, seed_hi; /* as ctl[5], ctl[6]; the noise stream stays tok_override[slot] - 1, else the slot index */
-    int32_t reserved[2];    /* 0 */
+    float rep_penalty;      /* as fctl[0] with ctl[2] set; 0 (or 1): no penalty, the slot's logits are left bit for bit */
+    int32_t suppress_steps; /* as ctl[1], and > 0 also as ctl[7]: the prompt pass's sample and every sample while step <
+                               suppress_steps never take 280 / 486 / EOS; 0: no suppression */
 } gsv_t2s_slot_sampling;
 int gsv_t2s_set_slot_sampling(gsv_t2s* h, int batch, gsv_t2s_slot_sampling* table);
 /* Writes table[slots[r]] = entries[r] on `stream`; slots / entries are HOST arrays [nrows] that ride in the kernel arguments (no
- * host-to-device copy between two decode windows).  GSV_ERR_STATE without a table; GSV_ERR_ARG for a slot out of range or a
- * sample_mode other than 0 / 2. */
+ * host-to-device copy between two decode windows).  GSV_ERR_STATE without a table; GSV_ERR_ARG for a slot out of range, a
+ * sample_mode other than 0 / 2, a negative or non-finite rep_penalty or negative suppress_steps. */
 int gsv_t2s_put_slot_sampling(gsv_t2s* h, int batch, const int32_t* slots, const gsv_t2s_slot_sampling* entries, int nrows,
                               void* stream);
+
+/* The repetition-penalty set of slots that take a request, in ONE launch on `stream`: for each row r, seen[slots[r]] is cleared
+ * and then seen[slots[r]][t] = 1 for every t in tokens[offsets[r] .. offsets[r + 1]) (the request's prompt tokens, which the
+ * reference penalises together with the generated ones, t2s_model.py:418-420; ids outside [0, vocab) are ignored).  slots
+ * [nrows <= 64, distinct] and offsets [nrows + 1, non-decreasing] are HOST arrays that ride in the kernel arguments; tokens is a
+ * packed DEVICE array (may be NULL when no row has tokens).  A row without tokens only clears: that is how a slot whose new
+ * request does not penalise gets rid of its previous tenant's set.  Call it before the request's prompt pass, in the state and on
+ * the stream that pass runs in (see gsv_t2s_set_slot_sampling: ORDER). */
+int gsv_t2s_seed_seen(gsv_t2s* h, int batch, const int32_t* slots, const int64_t* tokens, const int32_t* offsets, int nrows,
+                      void* stream);
 
 /* replaces process_single_data / process_batch_data (t2s_model.py:300-383): builds packed rows
  * [x_b | y_b | 0-pad] = text-emb + bert_proj + alpha_t*pe, audio-emb + alpha_a*pe.
@@ -183,7 +204,8 @@ int gsv_t2s_commit_slots(gsv_t2s* h, int batch, const int32_t* slots, int nrows,
  * NEXT requests into it with gsv_t2s_prefill_slots_staged on a side stream, several requests per pass, while the steps of
  * `batch_dst` run.  When a slot of `batch_dst` has finished, this call -- on the step's stream, after the pass's completion
  * event -- copies K/V rows [0, kv_len) of source slot slots_src[r] into slot slots_dst[r] and moves the staged kv_len,
- * x_len, step, eos_at, first logits / hidden / pending token into the live state of slots_dst[r]; the next step decodes it.
+ * x_len, step, eos_at, first logits / hidden / pending token into the live state of slots_dst[r], and the source slot's `seen`
+ * row (the set the pass penalised its first sample against) into seen[slots_dst[r]]; the next step decodes it.
  * slots_dst / slots_src / tok_override are HOST arrays [nrows] (they ride in the kernel arguments); tok_override (may be
  * NULL) sets state.tok_override[slots_dst[r]] (device sampling: the request's noise stream).  A prompt pass is
  * row-independent and packing-invariant, so a request's tokens do not depend on when or beside what it was prefilled. */
