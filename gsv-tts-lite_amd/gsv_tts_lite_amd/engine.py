@@ -76,7 +76,7 @@ class RequestSource:
 
     def fair_share(self) -> int:
         """How many more requests this rank may take AHEAD of its free slots without starving the others: what is left of the
-        queue over the ranks that pull from it, rounded up.  A rank that prefills ahead (t2s._infer_batched_ahead) asks before each
+        queue over the ranks that pull from it, rounded up.  A rank that prefills ahead (slot_loop.AheadLoop) asks before each
         packed prompt pass; without the cap one rank could hold `refill_ahead` requests of the queue's tail while other ranks'
         slots sit empty.  One read of the shared cursor (`add(key, 0)`), once per pass."""
         if self.store is None:

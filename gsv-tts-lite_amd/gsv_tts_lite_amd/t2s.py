@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import slot_loop as SL
 from . import slot_sampling as SS
 
 
@@ -60,6 +61,24 @@ def _sine_pe(n_pos, dim):
     return pe
 
 
+def state_spec(S, T, vocab, dim):
+    """the small tensors of a decode state of S slots with T cache rows, beside its K/V cache: (key of the `rt` dict, shape, dtype)"""
+    return [("kv_len", (S,), torch.int64), ("x_len", (S,), torch.int64), ("pre_tokens", (S, T + 1), torch.int64),
+            ("seen", (S, vocab), torch.uint8), ("step", (S,), torch.int32), ("eos_at", (S,), torch.int32),
+            ("logits", (S, vocab), torch.float32), ("hidden", (S, dim), torch.float32),
+            ("tok_override", (S,), torch.int64), ("ctl", (8,), torch.int32), ("fctl", (4,), torch.float32)]
+
+
+STATE_INIT = {"eos_at": -1, "fctl": 1.0}        # every other tensor starts at zero
+STATE_FIELD = {"k": "k_cache", "v": "v_cache", **{key: key for key, _, _ in state_spec(1, 1, 1, 1)}}   # state key -> gsv_t2s_state field
+
+
+def state_struct(batch, max_kv, ptrs):
+    """the C ABI's gsv_t2s_state from {state key: device pointer}: every pointer goes to the field of its name"""
+    by_field = {STATE_FIELD[key]: p for key, p in ptrs.items()}
+    return N.T2SState(batch=batch, max_kv=max_kv, **{f: by_field[f] for f, _ in N.T2SState._fields_[2:]})
+
+
 class Text2SemanticDecoder:
     def __init__(self, config):
         m = config["model"]
@@ -86,6 +105,13 @@ class Text2SemanticDecoder:
         self._weights = None
         self._h = None
         self._rt = {}
+        self._ws = self._ws_staged = None           # workspaces of the prompt passes: the current stream's, the refill stream's
+        self._ahead, self._tails = None, {}         # the bound states of `_ahead_state` / `_tail_state`
+        self._refill_stream = self._step_stream = None
+        self._in_step_stream = False
+        self._samp = None           # the RequestSampling of the infer_batched call that is running, or None (one set per call)
+        self._samp_bound = []       # states whose table is bound for it
+        self.sampling_binds = 0
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd):
@@ -96,63 +122,13 @@ class Text2SemanticDecoder:
         return self
 
     # ------------------------------------------------------------------ runtime
-    _RUNTIME_FIELDS = ("_h", "k_cache_root", "v_cache_root", "_rt", "cuda_graph_buckets", "batched_min", "_ws", "_ws_staged", "_ahead")
-
     @torch.inference_mode()
-    def initialize_runtime(self, dtype, device, gpt_cache, tune_placement=None):
-        """t2s_model.py:210-298 (`_build_runtime`).  `tune_placement` > 1 (GSV_TUNE_PLACEMENT; default off) is a diagnostic:
-        that many instances are built, each timed on 40 replays of its smallest batch size's step, the fastest kept.  It was the
-        default while a handle's ~450 buffers came from separate allocations and one instance in four decoded 3-9 % slower;
-        the library's per-handle arena (64 KB sub-allocation alignment, gsv_abi.hip) and the one-block state below put every
-        instance at the best time, so a load builds ONE runtime."""
-        if tune_placement is None:
-            tune_placement = int(os.environ.get("GSV_TUNE_PLACEMENT", "1"))
-        if tune_placement <= 1:
-            return self._build_runtime(dtype, device, gpt_cache)
-        cands = []
-        try:
-            for _ in range(tune_placement):
-                self.cuda_graph_buckets, self._rt, self._ws, self._ws_staged, self._h, self._ahead, self._tails = {}, {}, None, None, None, None, {}
-                self._build_runtime(dtype, device, gpt_cache)
-                cands.append((self._time_step(min(self._rt)), {k: getattr(self, k) for k in self._RUNTIME_FIELDS}))
-                self._h = None
-        finally:                      # also when a build raised half way: every handle but the kept one is released
-            if self._h is not None:   # the instance whose build or timing raised
-                N.lib().gsv_t2s_destroy(self._h)
-                self._h = None
-            cands.sort(key=lambda c: c[0])
-            for _, fields in cands[1:]:
-                N.lib().gsv_t2s_destroy(fields["_h"])
-            if cands:
-                for k, v in cands[0][1].items():
-                    setattr(self, k, v)
-        self.placement_times_ms = [c[0] for c in cands]
-        torch.cuda.synchronize(self.device)
-
-    def _time_step(self, batch):
-        """ms per decode step of this instance at `batch` sequences: hipGraph replay behind a prompt of about a quarter of the
-        cache, so that the K/V rows a real run reads are the ones the probe reads"""
-        rt, dev = self._rt[batch], self.device
-        lp = max(1, min(100, rt["T"] // 4))
-        one = torch.ones(lp, dtype=torch.int64, device=dev)
-        bert = torch.zeros(lp, 1024, dtype=torch.float32, device=dev)
-        self._set_ctl(rt, 0, 0, False, 1.0)
-        rt["kv_len"].zero_(); rt["x_len"].zero_()
-        xy, xl, yl, _, _ = self.embed_prompt([one] * batch, [one] * batch, [bert] * batch)
-        self.prefill(batch, 0, xy, xl, yl)
-        n = max(8, min(40, rt["T"] - 8))
-        self._decode(batch, 3)
-        torch.cuda.synchronize(dev)
-        import time
-        t0 = time.perf_counter()
-        self._decode(batch, n)
-        torch.cuda.synchronize(dev)
-        return (time.perf_counter() - t0) * 1e3 / n
-
-    def _build_runtime(self, dtype, device, gpt_cache):
-        """t2s_model.py:210-298.  Builds the native handle, uploads/repacks weights, allocates the
+    def initialize_runtime(self, dtype, device, gpt_cache):
+        """t2s_model.py:210-298 (`_build_runtime`).  Builds the native handle, uploads/repacks weights, allocates the
         nested KV cache (one root K and V; per batch size a [L,B,H,T,Dh] view; smaller buckets
-        are prefix slices on T) and binds one state per batch size."""
+        are prefix slices on T) and binds one state per batch size.  A load builds ONE runtime: the library's per-handle
+        arena (64 KB sub-allocation alignment, gsv_abi.hip) and the one-block state below put every instance at the best
+        step time (tools/placement_ab.py measures the spread between instances)."""
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("the MI355X hot path needs a GPU device (got %s); there is no CPU fallback" % device)
@@ -195,44 +171,41 @@ class Text2SemanticDecoder:
             ts = sorted(self.cuda_graph_buckets[b])
             T = ts[-1]
             n = self.num_layers * b * T * self.model_dim
-            # the step's state lives in ONE block, every tensor on a 64 KB boundary: where the small ones land relative to
-            # each other then never depends on what torch's caching allocator has free (the placement lottery of DESIGN 7)
-            spec = [("kv_len", (b,), torch.int64), ("x_len", (b,), torch.int64), ("pre_tokens", (b, T + 1), torch.int64),
-                    ("seen", (b, self.vocab_size), torch.uint8), ("step", (b,), torch.int32), ("eos_at", (b,), torch.int32),
-                    ("logits", (b, self.vocab_size), torch.float32), ("hidden", (b, self.model_dim), torch.float32),
-                    ("tok_override", (b,), torch.int64), ("ctl", (8,), torch.int32), ("fctl", (4,), torch.float32)]
-            al = 65536
-            offs, pos = [], 0
-            for _, shp, dt in spec:
-                offs.append(pos)
-                pos += -(-(int(np.prod(shp)) * torch.empty(0, dtype=dt).element_size()) // al) * al
-            separate = os.environ.get("GSV_STATE_SEPARATE") == "1"      # tools/placement_ab.py: the pre-round-3 layout
-            block = torch.zeros(pos + al, dtype=torch.uint8, device=device)
-            base = (-block.data_ptr()) % al
-            rt = {
-                "batch": b, "T": T, "_state_block": block,
-                "k": self.k_cache_root[:n].view(self.num_layers, b, self.num_head, T, dh),
-                "v": self.v_cache_root[:n].view(self.num_layers, b, self.num_head, T, dh),
-            }
-            for (name, shp, dt), o in zip(spec, offs):
-                nb = int(np.prod(shp)) * torch.empty(0, dtype=dt).element_size()
-                rt[name] = torch.zeros(*shp, dtype=dt, device=device) if separate else block[base + o: base + o + nb].view(dt).view(*shp)
-            rt["eos_at"].fill_(-1)
-            rt["fctl"].fill_(1.0)
-            st = N.T2SState(b, T, *[rt[k].data_ptr() for k in (
-                "k", "v", "kv_len", "x_len", "pre_tokens", "seen", "step", "eos_at", "logits", "hidden",
-                "tok_override", "ctl", "fctl")])
-            N.check(L.gsv_t2s_bind_state(h, ctypes.byref(st)))
+            rt = self._new_state(b, T, self.k_cache_root[:n].view(self.num_layers, b, self.num_head, T, dh),
+                                 self.v_cache_root[:n].view(self.num_layers, b, self.num_head, T, dh),
+                                 one_block=os.environ.get("GSV_STATE_SEPARATE") != "1")      # =1: tools/placement_ab.py, the pre-round-3 layout
             if b == 1:   # single-sequence loop: the EOS flag is read from a host-mapped mirror, not copied per window
                 rt["eos_host"] = torch.full((b,), -1, dtype=torch.int32).pin_memory()
                 N.check(L.gsv_t2s_set_eos_mirror(h, b, rt["eos_host"].data_ptr()))
             self._rt[b] = rt
             self.cuda_graph_buckets[b] = [Bucket(b, t, rt) for t in ts]
-        self._ws = None
-        self._ws_staged = None
-        self._ahead = None
-        self._tails = {}
         torch.cuda.synchronize(device)
+
+    def _new_state(self, S, T, k, v, one_block=False, **own):
+        """allocates the small tensors of a decode state of S slots with T cache rows over the K/V tensors given, binds it to the
+        handle and returns its `rt` dict (`own`: further entries).  one_block: the tensors live in ONE block, each on a 64 KB
+        boundary, so where they land relative to each other never depends on what torch's caching allocator has free (the
+        placement lottery of DESIGN 7); otherwise they are separate allocations."""
+        dev = self.device
+        spec = state_spec(S, T, self.vocab_size, self.model_dim)
+        rt = {"batch": S, "T": T, "k": k, "v": v, **own}
+        if one_block:
+            al = 65536
+            size = [-(-(math.prod(shp) * dt.itemsize) // al) * al for _, shp, dt in spec]
+            rt["_state_block"] = block = torch.zeros(sum(size) + al, dtype=torch.uint8, device=dev)
+            pos = (-block.data_ptr()) % al
+            for (key, shp, dt), nb in zip(spec, size):
+                rt[key] = block[pos: pos + math.prod(shp) * dt.itemsize].view(dt).view(*shp)
+                pos += nb
+        else:
+            for key, shp, dt in spec:
+                rt[key] = torch.zeros(*shp, dtype=dt, device=dev)
+        for key, value in STATE_INIT.items():
+            rt[key].fill_(value)
+        st = state_struct(S, T, {key: rt[key].data_ptr() for key in STATE_FIELD})
+        torch.cuda.synchronize(dev)       # binding may re-allocate the handle's scratch: nothing may be running on it
+        N.check(N.lib().gsv_t2s_bind_state(self._h, ctypes.byref(st)))
+        return rt
 
     def __del__(self):
         try:
@@ -319,7 +292,7 @@ class Text2SemanticDecoder:
         need = L.gsv_t2s_prefill_workspace(self._h, n, lmax)
         with torch.cuda.stream(torch.cuda.ExternalStream(stream_ptr, device=self.device)):
             # its own workspace, allocated on ITS stream: the prompt pass of the main stream (self._ws) may be running
-            if getattr(self, "_ws_staged", None) is None or self._ws_staged.numel() < need:
+            if self._ws_staged is None or self._ws_staged.numel() < need:
                 self._ws_staged = torch.empty(need, dtype=torch.uint8, device=self.device)
         ws = self._ws_staged
         N.check(L.gsv_t2s_prefill_slots_staged(self._h, batch, sl.data_ptr(), n, lmax, xy.data_ptr(), xl.data_ptr(), yl.data_ptr(),
@@ -331,7 +304,7 @@ class Text2SemanticDecoder:
         into the slot that takes the request.  Its batch size must differ from every stepped family's (states are keyed by it)
         and its cache is its own memory (the families' caches alias one root)."""
         key = (n_slots, max_kv)
-        sh = getattr(self, "_ahead", None)
+        sh = self._ahead
         if sh is not None and sh["key"] == key:
             return sh
         if sh is not None:                    # a state of another shape: the handle must not keep pointers into tensors about to go
@@ -341,25 +314,14 @@ class Text2SemanticDecoder:
         S = n_slots
         while S in self._rt:
             S += 1
-        dev, dh = self.device, self.model_dim // self.num_head
+        self._ahead = self._new_state(S, max_kv, *self._own_kv(S, max_kv), key=key, slots=n_slots)
+        return self._ahead
+
+    def _own_kv(self, S, max_kv):
+        """K and V cache of a state that does not alias the families' root"""
         kv_dtype = torch.bfloat16 if self.dtype == torch.float8_e4m3fn else self.dtype
-        spec = [("kv_len", (S,), torch.int64), ("x_len", (S,), torch.int64), ("pre_tokens", (S, max_kv + 1), torch.int64),
-                ("seen", (S, self.vocab_size), torch.uint8), ("step", (S,), torch.int32), ("eos_at", (S,), torch.int32),
-                ("logits", (S, self.vocab_size), torch.float32), ("hidden", (S, self.model_dim), torch.float32),
-                ("tok_override", (S,), torch.int64), ("ctl", (8,), torch.int32), ("fctl", (4,), torch.float32)]
-        rt = {"batch": S, "T": max_kv, "key": key, "slots": n_slots,
-              "k": torch.zeros(self.num_layers, S, self.num_head, max_kv, dh, dtype=kv_dtype, device=dev),
-              "v": torch.zeros(self.num_layers, S, self.num_head, max_kv, dh, dtype=kv_dtype, device=dev)}
-        for name, shp, dt in spec:
-            rt[name] = torch.zeros(*shp, dtype=dt, device=dev)
-        rt["eos_at"].fill_(-1)
-        rt["fctl"].fill_(1.0)
-        st = N.T2SState(S, max_kv, *[rt[k].data_ptr() for k in (
-            "k", "v", "kv_len", "x_len", "pre_tokens", "seen", "step", "eos_at", "logits", "hidden", "tok_override", "ctl", "fctl")])
-        torch.cuda.synchronize(dev)       # binding may re-allocate the handle's scratch: nothing may be running on it
-        N.check(N.lib().gsv_t2s_bind_state(self._h, ctypes.byref(st)))
-        self._ahead = rt
-        return rt
+        shape = (self.num_layers, S, self.num_head, max_kv, self.model_dim // self.num_head)
+        return torch.zeros(shape, dtype=kv_dtype, device=self.device), torch.zeros(shape, dtype=kv_dtype, device=self.device)
 
     def adopt_slots(self, batch, slots, src_batch, src_slots, tok_override=None):
         """gsv_t2s_adopt_slots on the current stream; the slot lists are host lists (they ride in the kernel arguments)"""
@@ -378,37 +340,20 @@ class Text2SemanticDecoder:
 
     def _tail_state(self, n_slots, max_kv):
         """a bound state of (about) `n_slots` slots with a K/V cache of its own that IS stepped: where the last live requests of a
-        continuous-batching run continue once the queue is empty (`_infer_batched_ahead`, gsv_t2s_move_slots).  Its batch size
+        continuous-batching run continue once the queue is empty (slot_loop.AheadLoop, gsv_t2s_move_slots).  Its batch size
         differs from every other bound state's (states are keyed by it): `n_slots`, or the next smaller free one."""
-        tails = self.__dict__.setdefault("_tails", {})
         key = (n_slots, max_kv)
-        if key in tails:
-            return tails[key]
+        if key in self._tails:
+            return self._tails[key]
         S = n_slots
-        taken = set(self._rt) | ({self._ahead["batch"]} if getattr(self, "_ahead", None) else set())
+        taken = set(self._rt) | ({self._ahead["batch"]} if self._ahead else set())
         while S in taken and S > 1:
             S -= 1
         if S in taken:
             return None
-        dev, dh = self.device, self.model_dim // self.num_head
-        kv_dtype = torch.bfloat16 if self.dtype == torch.float8_e4m3fn else self.dtype
-        spec = [("kv_len", (S,), torch.int64), ("x_len", (S,), torch.int64), ("pre_tokens", (S, max_kv + 1), torch.int64),
-                ("seen", (S, self.vocab_size), torch.uint8), ("step", (S,), torch.int32), ("eos_at", (S,), torch.int32),
-                ("logits", (S, self.vocab_size), torch.float32), ("hidden", (S, self.model_dim), torch.float32),
-                ("tok_override", (S,), torch.int64), ("ctl", (8,), torch.int32), ("fctl", (4,), torch.float32)]
-        rt = {"batch": S, "T": max_kv, "key": key, "tail": True,
-              "k": torch.zeros(self.num_layers, S, self.num_head, max_kv, dh, dtype=kv_dtype, device=dev),
-              "v": torch.zeros(self.num_layers, S, self.num_head, max_kv, dh, dtype=kv_dtype, device=dev)}
-        for name, shp, dt in spec:
-            rt[name] = torch.zeros(*shp, dtype=dt, device=dev)
-        rt["eos_at"].fill_(-1)
-        rt["fctl"].fill_(1.0)
-        st = N.T2SState(S, max_kv, *[rt[k].data_ptr() for k in (
-            "k", "v", "kv_len", "x_len", "pre_tokens", "seen", "step", "eos_at", "logits", "hidden", "tok_override", "ctl", "fctl")])
-        torch.cuda.synchronize(dev)       # binding may re-allocate the handle's scratch: nothing may be running on it
-        N.check(N.lib().gsv_t2s_bind_state(self._h, ctypes.byref(st)))
+        rt = self._new_state(S, max_kv, *self._own_kv(S, max_kv), key=key, tail=True)
         self._rt[S] = rt                  # stepped like a family's state (`_decode` / `_flush` look it up); not a KV bucket family
-        tails[key] = rt
+        self._tails[key] = rt
         return rt
 
     def commit_slots(self, batch, sl):
@@ -436,8 +381,8 @@ class Text2SemanticDecoder:
             rt["samp"].zero_()
         torch.cuda.synchronize(self.device)     # the state's captured steps go: none of them may be running
         N.check(N.lib().gsv_t2s_set_slot_sampling(self._h, rt["batch"], rt["samp"].data_ptr()))
-        self._samp_bound = self._samp_bound + [rt]
-        self.sampling_binds = getattr(self, "sampling_binds", 0) + 1
+        self._samp_bound.append(rt)
+        self.sampling_binds += 1
 
     def _unbind_sampling(self):
         torch.cuda.synchronize(self.device)
@@ -489,9 +434,6 @@ class Text2SemanticDecoder:
         """tok_override of a slot that takes request c under device sampling: its noise stream + 1"""
         return c + 1 if self._samp is None else self._samp.stream(c)
 
-    _samp = None            # the RequestSampling of the infer_batched call that is running, or None (one set per call)
-    _samp_bound = []        # states whose table is bound for it
-
     def _set_ctl(self, rt, mode, suppress_steps, rep_enabled, rep, top_k=0, temperature=1.0, seed=0, top_p=1.0,
                  suppress_first=False):
         """mode 0 = greedy on device, 2 = device sampling (1, host-sampled tokens through tok_override, is the C ABI's and unused here); suppress_first: the
@@ -516,22 +458,17 @@ class Text2SemanticDecoder:
 
     # ------------------------------------------------------------------ drivers
     @torch.inference_mode()
-    def infer(self, x, y, bert_feature, top_k: int = 15, top_p: float = 1.0, temperature: float = 1.0,
-              repetition_penalty: float = 1.35, initial_suppression_steps: int = 10, check_interval: int = 5,
-              generator=None, max_new_tokens: int = None):
-        """t2s_model.py:385-464.  x int64[1,Lx], y int64[1,Ly], bert [1,Lx,1024] -> int64[1,1,N].
-        `max_new_tokens` (not in the reference, whose only length limit is the largest bucket) caps the loop."""
+    def _begin_single(self, x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, initial_suppression_steps, generator):
+        """what `infer` and `infer_stream` do up to the first decode step (t2s_model.py:385-417): control words, the penalty set
+        seeded with the prompt's tokens, the prompt pass.  Returns (rt, prompt length, decode iterations the largest bucket leaves)."""
         rt = self._rt[1]
-        buckets = self.cuda_graph_buckets[1]
-        lx, ly = int(x.shape[1]), int(y.shape[1])
-        Lp = lx + ly
-        if Lp > buckets[-1].max_kv_cache:
-            raise ValueError("prompt of %d positions exceeds the largest KV bucket (%d)" % (Lp, buckets[-1].max_kv_cache))
-        n_iter = buckets[-1].max_kv_cache - Lp
+        max_kv = self.cuda_graph_buckets[1][-1].max_kv_cache
+        Lp = int(x.shape[1]) + int(y.shape[1])
+        if Lp > max_kv:
+            raise ValueError("prompt of %d positions exceeds the largest KV bucket (%d)" % (Lp, max_kv))
+        n_iter = max_kv - Lp
         if n_iter < 1:
             raise RuntimeError("no decode iterations: prompt fills the largest bucket")
-        if max_new_tokens is not None:
-            n_iter = max(1, min(n_iter, int(max_new_tokens)))
         mode, seed = self._sampling_mode(top_k, top_p, generator)
         rep_on = repetition_penalty != 1.0
         self._set_ctl(rt, mode, initial_suppression_steps, rep_on, repetition_penalty, top_k, temperature, seed, top_p,
@@ -543,6 +480,18 @@ class Text2SemanticDecoder:
             rt["seen"][0, y[0].to(self.device)] = 1
         xy, xl, yl, _, _ = self.embed_prompt([x[0]], [y[0]], [bert_feature[0]])
         self.prefill(1, 0, xy, xl, yl)
+        return rt, Lp, n_iter
+
+    @torch.inference_mode()
+    def infer(self, x, y, bert_feature, top_k: int = 15, top_p: float = 1.0, temperature: float = 1.0,
+              repetition_penalty: float = 1.35, initial_suppression_steps: int = 10, check_interval: int = 5,
+              generator=None, max_new_tokens: int = None):
+        """t2s_model.py:385-464.  x int64[1,Lx], y int64[1,Ly], bert [1,Lx,1024] -> int64[1,1,N].
+        `max_new_tokens` (not in the reference, whose only length limit is the largest bucket) caps the loop."""
+        rt, Lp, n_iter = self._begin_single(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty,
+                                            initial_suppression_steps, generator)
+        if max_new_tokens is not None:
+            n_iter = max(1, min(n_iter, int(max_new_tokens)))
         done = 0
         eos_at = -1
         # The reference tests for EOS on the host every `check_interval` steps (t2s_model.py:451-453).  Same
@@ -569,11 +518,7 @@ class Text2SemanticDecoder:
             k ^= 1
             ev.record()
             if pending is not None:
-                if os.environ.get("GSV_EV_SPIN"):
-                    while not pending.query():
-                        pass
-                else:
-                    pending.synchronize()
+                pending.synchronize()
                 # the mirror may already hold an EOS of the window enqueued AFTER the one just waited for (the GPU runs
                 # ahead of this read): only an EOS recorded by a step of the waited-for windows counts, so the number of
                 # windows a run executes -- and with it the state it leaves behind -- does not depend on timing
@@ -597,27 +542,8 @@ class Text2SemanticDecoder:
         boost_first_chunk), EOS is never part of a chunk, and the final chunk after an EOS is the last `idx`
         entries of y ++ samples, i.e. it starts with the first sample s0 that infer() drops.  The decode steps
         run on device in groups of <= 5 (greedy / device sampling); a group that runs past the EOS is harmless."""
-        with torch.inference_mode():
-            rt = self._rt[1]
-            buckets = self.cuda_graph_buckets[1]
-            lx, ly = int(x.shape[1]), int(y.shape[1])
-            Lp = lx + ly
-            if Lp > buckets[-1].max_kv_cache:
-                raise ValueError("prompt of %d positions exceeds the largest KV bucket (%d)" % (Lp, buckets[-1].max_kv_cache))
-            n_iter = buckets[-1].max_kv_cache - Lp
-            if n_iter < 1:
-                raise RuntimeError("no decode iterations: prompt fills the largest bucket")
-            mode, seed = self._sampling_mode(top_k, top_p, generator)
-            rep_on = repetition_penalty != 1.0
-            self._set_ctl(rt, mode, initial_suppression_steps, rep_on, repetition_penalty, top_k, temperature, seed, top_p,
-                          suppress_first=True)
-            rt["seen"].zero_()
-            if mode == 2:
-                rt["tok_override"].zero_()
-            if rep_on:
-                rt["seen"][0, y[0].to(self.device)] = 1
-            xy, xl, yl, _, _ = self.embed_prompt([x[0]], [y[0]], [bert_feature[0]])
-            self.prefill(1, 0, xy, xl, yl)
+        rt, Lp, n_iter = self._begin_single(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty,
+                                            initial_suppression_steps, generator)
         done, first, pre_chunk = 0, True, None
         while done < n_iter:
             with torch.inference_mode():
@@ -646,444 +572,6 @@ class Text2SemanticDecoder:
             with torch.inference_mode():
                 final = rt["pre_tokens"][0, Lp + 1: Lp + 1 + n_iter].clone()
         yield final[None, None], True
-
-    @torch.inference_mode()
-    def _infer_batched_staged(self, x, y, bert_feature, B, first, nxt, exhausted, first_len, check_interval, on_finish,
-                              max_new_tokens, stream_by_request=False):
-        """The slot loop of t2s_model.py:555-734 with nothing on the decode steps' critical path but the steps:
-
-          * a finished slot is PARKED (kv_len = -1: the step leaves its rows and state alone and attends over one row),
-            its prompt pass runs on a side stream into the live K/V rows and the library's staging, and it joins at the
-            first window boundary after the pass has completed (gsv_t2s_prefill_slots_staged / gsv_t2s_commit_slots);
-          * the host never waits for the window it has just issued: the per-window read-back (kv_len, eos_at) is an
-            asynchronous copy examined one window later, while the next window runs.  Ends the host can predict --
-            a token budget, a full cache -- park the slot with no lag; an EOS is seen one window (<= 5 garbage steps
-            of that slot) late.  Tokens are cut at the first EOS from the device's `eos_at`, so the lag never shows.
-
-        Which request a slot gets is decided when the slot is parked, rows are independent through every kernel, so every
-        request's tokens equal the reference-order loop's (tests/test_hip_t2s.py); completion ORDER and the window a
-        request joins at depend on timing.  A request that fills the cache is cut at the largest bucket's limit
-        (kv + check_interval >= max_kv at a window boundary), as in the reference's last bucket.
-        The prefill of `first` into slots 0.. has already run on the current stream."""
-        rt = self._rt[B]
-        dev = self.device
-        cap = max(b.max_kv_cache for b in self.cuda_graph_buckets[B])
-        if getattr(self, "_refill_stream", None) is None:
-            self._refill_stream = torch.cuda.Stream(device=dev, priority=self.refill_priority)
-        side = self._refill_stream
-        main = torch.cuda.current_stream(dev)
-        # the requests' inputs (phoneme ids, prompt tokens, BERT rows) were produced on the caller's stream; the side stream
-        # reads them in embed_prompt BEFORE it waits on any step.  One event orders the inputs, not the steps.
-        inputs_ready = torch.cuda.Event()
-        inputs_ready.record(main)
-        side.wait_event(inputs_ready)
-        LIVE, PARKED, IDLE = 0, 1, 2
-        actual = len(first)
-        state = [LIVE] * actual + [IDLE] * (B - actual)
-        req = list(first) + [-1] * (B - actual)
-        start = list(first_len) + [0] * (B - actual)       # kv_len the slot joined with (its prompt length)
-        steps = [0] * B                                     # steps issued since the slot joined
-        joined = [0] * B                                    # first window whose read-back shows the slot's current request
-        if actual < B:
-            rt["kv_len"][actual:] = -1
-        pred, orig = [], []
-        waiting: list = []      # (slot, request): parked, prompt pass not launched yet
-        waiting_since = [0]     # window at which the oldest of them was parked
-        window = 0
-        inflight: list = []     # at most one staged prompt pass: (slots, device slot list, done event, keep-alive tensors)
-        to_cut: list = []       # (window, slot, request, first row, most tokens): parked, tokens not collected yet
-        snap_host = torch.empty((2, 2, B), dtype=torch.int64).pin_memory()
-        snaps: list = []        # (window, buffer, event)
-        self.last_stats = {"slots": B, "steps": 0, "kv_rows": 0, "prefill_rows": actual, "refills": 0}
-
-        def park(i):
-            """slot i has finished (or has nothing to do): park it, and give it the next request if there is one"""
-            nonlocal exhausted
-            rt["kv_len"][i] = -1
-            cur = None if exhausted else nxt()
-            if cur is None:
-                exhausted = True
-                state[i] = IDLE
-                return
-            n_new = int(x[cur].shape[0]) + int(y[cur].shape[0])
-            if n_new > cap - 1:
-                raise ValueError("prompt longer than the largest KV bucket")
-            state[i], req[i] = PARKED, cur
-            waiting.append((i, cur, n_new))
-            if len(waiting) == 1:
-                waiting_since[0] = window
-
-        def collect(i, r, a0, n_keep):
-            seg = rt["pre_tokens"][i, a0: a0 + max(0, n_keep)].clone()
-            pred.append(seg)
-            orig.append(r)
-            if on_finish is not None:
-                on_finish(r, seg)
-
-        def launch_refill(force=False):
-            if inflight or not waiting:
-                return
-            # a prompt pass is ~120 launches whatever its row count and takes its share of the chip from the steps: a lone
-            # request waits one window for company (costs 1/B of a window's tokens, saves most of a pass)
-            if not force and len(waiting) < self.refill_group and window - waiting_since[0] < self.refill_wait:
-                return
-            group = waiting[:]
-            waiting.clear()
-            ev = torch.cuda.Event()
-            ev.record(main)         # the parking writes, and every step that still wrote these slots' rows
-            rq = [c for _, c, _ in group]
-            with torch.cuda.stream(side):
-                # the embedding and its host->device copies first: they depend on nothing the steps do, and a pageable
-                # copy blocks the host until its stream gets there -- it must not sit behind the wait on the steps
-                xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in rq], [y[c] for c in rq], [bert_feature[c] for c in rq])
-                sl = torch.tensor([i for i, _, _ in group], dtype=torch.int32, device=dev)
-                ids = torch.tensor([self._stream_id(c) for _, c, _ in group], dtype=torch.int64, device=dev)
-                seed = self._seed_tokens(rq, y)
-                side.wait_event(ev)
-                # the parked slots' penalty sets and table entries, behind the last step that recorded their previous tenants' tokens:
-                # the steps leave a parked slot's `seen` alone, and what they read of its entry goes nowhere
-                self._put_request(B, [i for i, _, _ in group], rq, seed)
-                self.prefill_slots_staged(B, sl, xy1, xl1, yl1, side.cuda_stream)
-                done = torch.cuda.Event()
-                done.record(side)
-            inflight.append((group, sl, done, (xy1, xl1, yl1, ids), window))
-            self.last_stats["refills"] += len(group)
-            self.last_stats["prefill_rows"] += len(group)
-
-        def join(window, block):
-            """a completed prompt pass joins: staging -> live state on the steps' stream"""
-            if not inflight:
-                return
-            group, sl, done, _keep, launched = inflight[0]
-            if block:
-                done.synchronize()
-            elif not done.query():
-                return
-            # the old occupants' tokens first: the pass started after the read-back of the window it was launched in, so
-            # those read-backs are on the host (no wait here), and the new request's steps will overwrite the rows
-            while snaps and snaps[0][0] <= launched:
-                examine(*snaps.pop(0))
-            assert not any(i == c[1] for c in to_cut for i, _, _ in group), "a slot joined before its tokens were collected"
-            main.wait_event(done)
-            self.commit_slots(B, sl)
-            sl.record_stream(main)      # allocated on the side stream's pool, read here by the steps' stream
-            if stream_by_request:       # device sampling: the joined slots draw from their requests' noise streams
-                rt["tok_override"].index_copy_(0, sl.long(), _keep[3])
-                _keep[3].record_stream(main)
-            for i, _, n_new in group:
-                state[i], steps[i], start[i], joined[i] = LIVE, 0, n_new, window
-            inflight.clear()
-
-        def examine(window, buf, ev):
-            """read-back of `window` (taken after its steps): collect what was parked at that boundary, find EOS ends"""
-            ev.synchronize()
-            kv_s, eos_s = snap_host[buf].tolist()
-            for rec in [c for c in to_cut if c[0] == window]:
-                _, i, r, a0, n_max = rec
-                e = eos_s[i]                               # index of the first EOS among the slot's samples, or -1
-                collect(i, r, a0, n_max if e < 1 else min(n_max, e - 1))
-                to_cut.remove(rec)
-            for i in range(B):
-                if state[i] == LIVE and joined[i] <= window and eos_s[i] >= 0:
-                    collect(i, req[i], start[i] + 1, eos_s[i] - 1)
-                    park(i)
-
-        idx = 0
-        while True:
-            if not any(st == LIVE for st in state):
-                while snaps:                        # nothing is running that the read-backs could hide behind
-                    examine(*snaps.pop(0))
-            join(window, block=not any(st == LIVE for st in state))
-            if not any(st == LIVE for st in state):
-                if waiting and not inflight:        # nothing left to overlap the prompt pass with
-                    launch_refill(force=True)
-                    continue
-                if inflight:
-                    continue
-                break
-            n = 1 if idx == 0 else min(check_interval, 1000 - idx)     # the reference's cadence: tests after steps 1, 6, 11, ...
-            self._decode(B, n)
-            self._flush(B)
-            idx = 0 if idx + n >= 1000 else idx + n
-            buf = window & 1
-            snap_host[buf].copy_(torch.stack([rt["kv_len"], rt["eos_at"].to(torch.int64)]), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self.last_stats["steps"] += n
-            for i in range(B):
-                if state[i] == LIVE:
-                    steps[i] += n
-                    self.last_stats["kv_rows"] += (start[i] + steps[i]) * n
-            # ends the host can tell without the device: park now (no garbage window), cut the tokens when this window's read-back is in
-            for i in range(B):
-                if state[i] != LIVE:
-                    continue
-                budget = None if max_new_tokens is None else int(max_new_tokens[req[i]])
-                full = start[i] + steps[i] + check_interval >= cap
-                if full or (budget is not None and steps[i] - 1 >= budget):
-                    n_max = steps[i] - 1 if budget is None else min(steps[i] - 1, budget)
-                    to_cut.append((window, i, req[i], start[i] + 1, n_max))
-                    park(i)
-            snaps.append((window, buf, ev))
-            launch_refill()                          # host work of a prompt pass: behind the steps the GPU is busy with
-            while len(snaps) > 1:                    # the PREVIOUS window's read-back: on the host by now
-                examine(*snaps.pop(0))
-            window += 1
-        for sn in snaps:
-            examine(*sn)
-        assert not to_cut and not waiting and not inflight
-        return pred, torch.tensor(orig, device=dev)
-
-    @torch.inference_mode()
-    def _infer_batched_ahead(self, x, y, bert_feature, B, first, nxt, exhausted, first_len, check_interval, on_finish,
-                             max_new_tokens, stream_by_request=False):
-        """The slot loop of t2s_model.py:555-734 with the prompt passes run AHEAD of the slots that will decode them.
-
-        `_infer_batched_staged` starts a request's prompt pass when a slot has finished: the slot idles for the pass and
-        for the windows around it (two to three windows of five steps per refill), and a pass carries the one or two
-        requests whose slots happened to finish together (a pass of one costs what a pass of two costs: ~120 dependent
-        launches).  Here up to `refill_ahead` of the NEXT requests are prefilled, several per pass, on a side stream into a
-        second bound state that is never stepped (`_ahead_state`); a slot that finishes at a window boundary takes a
-        finished one before the next window is issued (gsv_t2s_adopt_slots: its K/V rows and staged state move over, ~10 us)
-        and decodes on.  A prompt pass is row-independent and packing-invariant, so every request's tokens equal the
-        reference-order loop's (tests/test_hip_t2s.py); which slot and window a request gets depends on timing.
-        The window read-back, the budget / full-cache ends and the cut at the first EOS are the staged loop's."""
-        rt = self._rt[B]
-        dev = self.device
-        cap = max(b.max_kv_cache for b in self.cuda_graph_buckets[B])
-        sh = self._ahead_state(max(1, min(self.refill_ahead, B)), cap)
-        S = sh["slots"]
-        # tail compaction: bound BEFORE the first step (binding may re-allocate the handle's scratch), largest first
-        tails = [t for t in (self._tail_state(lv, cap) for lv in sorted(set(self.tail_levels), reverse=True) if lv < B) if t is not None]
-        B0 = B
-        if self._samp is not None:
-            # compaction carries a slot's entry to the tail state's table (gsv_t2s_move_slots).  The ahead state is never stepped,
-            # but its prompt passes penalise and suppress the first sample by ITS table and `seen`; the adopting state's token
-            # kernel draws that sample, so the entry goes into both (`top_up`, `fill`)
-            for t in tails + [sh]:
-                self._bind_sampling(t)
-        for k in ("ctl", "fctl"):
-            sh[k].copy_(rt[k])          # the prompt pass's first logits obey the same control words
-        if getattr(self, "_refill_stream", None) is None:
-            self._refill_stream = torch.cuda.Stream(device=dev, priority=self.refill_priority)
-        side = self._refill_stream
-        main = torch.cuda.current_stream(dev)
-        inputs_ready = torch.cuda.Event()
-        inputs_ready.record(main)       # the requests' inputs and the control words above
-        side.wait_event(inputs_ready)
-        LIVE, EMPTY = 0, 1
-        actual = len(first)
-        state = [LIVE] * actual + [EMPTY] * (B - actual)
-        req = list(first) + [-1] * (B - actual)
-        start = list(first_len) + [0] * (B - actual)
-        steps = [0] * B
-        joined = [0] * B
-        if actual < B:
-            rt["kv_len"][actual:] = -1
-        pred, orig = [], []
-        free_src = list(range(S))       # slots of the ahead state holding nothing
-        ready: list = []                # (source slot, request, prompt length, completion event of its pass), oldest first
-        inflight = [None]               # completion event of the one prompt pass that may be running
-        adopted_ev = [None]             # behind the last adopt: a later pass may overwrite the source slots it read
-        window = 0
-        to_cut: list = []               # (window, slot, request, saved tokens, most tokens)
-        snap_host = torch.empty((2, 2, B), dtype=torch.int64).pin_memory()
-        snaps: list = []
-        keep: list = []                 # tensors of the pass in flight
-        self.last_stats = {"slots": B, "steps": 0, "kv_rows": 0, "prefill_rows": actual, "refills": 0, "passes": 1,
-                           "slot_steps": 0, "live_slot_steps": 0, "compactions": []}
-
-        def compact():
-            """queue empty, nothing prefilled ahead: the live requests continue on the smallest tail state that holds them (the
-            reference keeps stepping the full batch, t2s_model.py:684-694).  Every outstanding window is read back first (its
-            records name slots of the state that is left)."""
-            nonlocal B, rt, state, req, start, steps, joined, snap_host
-            if not tails or not exhausted or ready:
-                return
-            if inflight[0] is not None:     # the last prompt pass: its requests are in `ready` until adopted; nothing else will come
-                if not inflight[0].query():
-                    return
-                inflight[0] = None
-                keep.clear()
-            n_live = sum(st == LIVE for st in state)
-            if n_live == 0 or not any(t["batch"] < B and t["batch"] >= n_live for t in tails):
-                return
-            while snaps:
-                examine(*snaps.pop(0))
-            live = [i for i in range(B) if state[i] == LIVE]
-            fit = [t for t in tails if t["batch"] < B and t["batch"] >= len(live)]
-            if not live or not fit:
-                return
-            dst = min(fit, key=lambda t: t["batch"])
-            nb = dst["batch"]
-            for k in ("ctl", "fctl"):
-                dst[k].copy_(rt[k])
-            dst["fused_ok"] = rt.get("fused_ok", False)
-            dst["kv_len"].fill_(-1)
-            self.move_slots(nb, list(range(len(live))), B, live)
-            self.last_stats["compactions"].append((window, B, nb, len(live)))
-            pad = nb - len(live)
-            state = [LIVE] * len(live) + [EMPTY] * pad
-            req = [req[i] for i in live] + [-1] * pad
-            start = [start[i] for i in live] + [0] * pad
-            steps = [steps[i] for i in live] + [0] * pad
-            joined = [0] * nb                # every outstanding window has been examined
-            B, rt = nb, dst
-            snap_host = torch.empty((2, 2, B), dtype=torch.int64).pin_memory()
-
-        def top_up(force=False):
-            """one packed prompt pass for the next requests, into the free slots of the ahead state"""
-            nonlocal exhausted
-            if exhausted or not free_src:
-                return
-            if inflight[0] is not None:
-                if force:
-                    inflight[0].synchronize()
-                elif not inflight[0].query():
-                    return
-                inflight[0] = None
-                keep.clear()
-            if not force and len(free_src) < max(1, S // 2) and ready:
-                return                  # a pass of few rows costs what a pass of many costs: wait until half the slots are free
-            # N ranks pull from one queue: near its end a rank takes ahead no more than its share of what is left
-            # (engine.RequestSource.fair_share), so the tail is not parked in one rank's ahead slots while others idle
-            share = getattr(getattr(nxt, "__self__", None), "fair_share", None)
-            quota = len(free_src) if share is None else max(1, min(len(free_src), share()))
-            group = []
-            while free_src and not exhausted and len(group) < quota:
-                cur = nxt()
-                if cur is None:
-                    exhausted = True
-                    break
-                n_new = int(x[cur].shape[0]) + int(y[cur].shape[0])
-                if n_new > cap - 1:
-                    raise ValueError("prompt longer than the largest KV bucket")
-                group.append((free_src.pop(0), cur, n_new))
-            if not group:
-                return
-            rq = [c for _, c, _ in group]
-            with torch.cuda.stream(side):
-                xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in rq], [y[c] for c in rq], [bert_feature[c] for c in rq])
-                sl = torch.tensor([i for i, _, _ in group], dtype=torch.int32, device=dev)
-                seed = self._seed_tokens(rq, y)
-                if adopted_ev[0] is not None:
-                    side.wait_event(adopted_ev[0])
-                self._put_request(sh["batch"], [i for i, _, _ in group], rq, seed)
-                self.prefill_slots_staged(sh["batch"], sl, xy1, xl1, yl1, side.cuda_stream)
-                done = torch.cuda.Event()
-                done.record(side)
-            keep.extend((xy1, xl1, yl1, sl))
-            inflight[0] = done
-            for i, c, n_new in group:
-                ready.append((i, c, n_new, done, window))
-            self.last_stats["refills"] += len(group)
-            self.last_stats["prefill_rows"] += len(group)
-            self.last_stats["passes"] += 1
-
-        def fill(block=False):
-            """empty slots take finished prompt passes, oldest first, before the next window is issued"""
-            empty = [i for i in range(B) if state[i] == EMPTY]
-            take = []
-            while empty and ready:
-                src, cur, n_new, done, launched = ready[0]
-                if not done.query():
-                    # the steps' stream may wait for a pass that has had a window to run (it ends inside the wait, if at all);
-                    # a younger one would stall every slot for most of its ~1 ms: the slot idles this window instead
-                    if not block and window - launched < 1:
-                        break
-                main.wait_event(done)
-                ready.pop(0)
-                take.append((empty.pop(0), src, cur, n_new))
-            if not take:
-                return
-            self.adopt_slots(B, [i for i, _, _, _ in take], sh["batch"], [s_ for _, s_, _, _ in take],
-                             [self._stream_id(c) for _, _, c, _ in take] if stream_by_request else None)
-            self._put_sampling(B, [i for i, _, _, _ in take], [c for _, _, c, _ in take])
-            ev = torch.cuda.Event()
-            ev.record(main)
-            adopted_ev[0] = ev
-            for i, src, cur, n_new in take:
-                state[i], req[i], steps[i], start[i], joined[i] = LIVE, cur, 0, n_new, window
-                free_src.append(src)
-
-        def collect(r, seg):
-            pred.append(seg)
-            orig.append(r)
-            if on_finish is not None:
-                on_finish(r, seg)
-
-        def vacate(i):
-            rt["kv_len"][i] = -1        # parked: the step leaves the slot's rows and state alone
-            state[i], req[i] = EMPTY, -1
-
-        def examine(window, buf, ev):
-            ev.synchronize()
-            kv_s, eos_s = snap_host[buf].tolist()
-            for rec in [c for c in to_cut if c[0] == window]:
-                _, i, r, saved, n_max = rec
-                e = eos_s[i]
-                collect(r, saved[: max(0, n_max if e < 1 else min(n_max, e - 1))].clone())
-                to_cut.remove(rec)
-            for i in range(B):
-                if state[i] == LIVE and joined[i] <= window and eos_s[i] >= 0:
-                    collect(req[i], rt["pre_tokens"][i, start[i] + 1: start[i] + 1 + max(0, eos_s[i] - 1)].clone())
-                    vacate(i)
-
-        top_up(force=True)
-        idx = 0
-        while True:
-            live = any(st == LIVE for st in state)
-            if not live:
-                while snaps:
-                    examine(*snaps.pop(0))
-            fill(block=not live)
-            live = any(st == LIVE for st in state)
-            if not live:
-                if ready:
-                    continue
-                top_up(force=True)
-                if ready:
-                    continue
-                break
-            compact()
-            if not any(st == LIVE for st in state):
-                continue
-            n = 1 if idx == 0 else min(check_interval, 1000 - idx)
-            self._decode(B, n)
-            self._flush(B)
-            self.last_stats["slot_steps"] += B * n
-            self.last_stats["live_slot_steps"] += n * sum(st == LIVE for st in state)
-            idx = 0 if idx + n >= 1000 else idx + n
-            buf = window & 1
-            snap_host[buf].copy_(torch.stack([rt["kv_len"], rt["eos_at"].to(torch.int64)]), non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self.last_stats["steps"] += n
-            for i in range(B):
-                if state[i] == LIVE:
-                    steps[i] += n
-                    self.last_stats["kv_rows"] += (start[i] + steps[i]) * n
-            for i in range(B):
-                if state[i] != LIVE:
-                    continue
-                budget = None if max_new_tokens is None else int(max_new_tokens[req[i]])
-                full = start[i] + steps[i] + check_interval >= cap
-                if full or (budget is not None and steps[i] - 1 >= budget):
-                    n_max = steps[i] - 1 if budget is None else min(steps[i] - 1, budget)
-                    # the slot may decode another request from the next window on: its tokens are saved now (behind this
-                    # window's steps on the stream), cut at the first EOS when the window's read-back is in
-                    saved = rt["pre_tokens"][i, start[i] + 1: start[i] + 1 + max(0, n_max)].clone()
-                    to_cut.append((window, i, req[i], saved, n_max))
-                    vacate(i)
-            snaps.append((window, buf, ev))
-            top_up()
-            while len(snaps) > 1:
-                examine(*snaps.pop(0))
-            window += 1
-        for sn in snaps:
-            examine(*sn)
-        assert not to_cut and not ready
-        return pred, torch.tensor(orig, device=dev)
 
     @torch.inference_mode()
     def infer_batched(self, x: List[torch.Tensor], y: List[torch.Tensor], bert_feature: List[torch.Tensor],
@@ -1116,8 +604,9 @@ class Text2SemanticDecoder:
         engine starts that utterance's vocoder work on a side stream while the slots keep decoding).
         `max_new_tokens` (a list indexed like x; not in the reference, which stops at EOS or a full cache only) ends
         request i once it has produced that many tokens -- tested at the same 5-step cadence as EOS, cut exactly.
-        `async_refill` (not in the reference, whose slots all wait while a refill's prompt pass runs, :696-722) runs the
-        slot loop of `_infer_batched_staged` instead: same requests, same tokens per request, no stall."""
+        `async_refill` (not in the reference, whose slots all wait while a refill's prompt pass runs, :696-722) runs an
+        asynchronous slot loop instead (slot_loop.AheadLoop; with GSV_REFILL_AHEAD=0 slot_loop.StagedLoop): same requests,
+        same tokens per request, no stall."""
         samp = SS.resolve(len(x), top_k, top_p, temperature, seed, repetition_penalty, initial_suppression_steps)
         if samp is None:
             return self._infer_batched_call(x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval,
@@ -1133,10 +622,10 @@ class Text2SemanticDecoder:
     def _infer_batched_call(self, x, y, bert_feature, top_k, top_p, temperature, repetition_penalty, check_interval, generator,
                             source, slots, on_finish, max_new_tokens, async_refill):
         """infer_batched behind the resolution of its sampling arguments (`self._samp`: per request, or None: the scalars here)"""
-        if async_refill and self.step_priority != 0 and not getattr(self, "_in_step_stream", False):
+        if async_refill and self.step_priority != 0 and not self._in_step_stream:
             # the slot loop on a stream of its own priority (the steps are a chain of short dependent launches: whatever a
             # launch waits for behind a prompt pass's blocks is on the critical path, the prompt pass itself is not)
-            if getattr(self, "_step_stream", None) is None:
+            if self._step_stream is None:
                 self._step_stream = torch.cuda.Stream(device=self.device, priority=self.step_priority)
             cur = torch.cuda.current_stream(self.device)
             self._step_stream.wait_stream(cur)
@@ -1206,111 +695,18 @@ class Text2SemanticDecoder:
             raise ValueError("prompt longer than the largest KV bucket")
         self._put_request(batch_size, range(actual), first, self._seed_tokens(first, y))
         self.prefill(batch_size, 0, xy, xl, yl)
-        rows = torch.arange(batch_size, device=dev)
         if mode == 2:       # device sampling: the noise stream of a slot is its REQUEST (placement-invariant samples)
             rt["tok_override"].zero_()
             rt["tok_override"][:actual] = torch.tensor([self._stream_id(c) for c in first], dtype=torch.int64, device=dev)
-        if async_refill:
-            try:
-                loop = self._infer_batched_ahead if self.refill_ahead > 0 else self._infer_batched_staged
-                return loop(x, y, bert_feature, batch_size, first, nxt, exhausted,
-                                                  [int(a) + int(b) for a, b in zip(x_lens_h, y_lens_h)], check_interval,
-                                                  on_finish, max_new_tokens, mode == 2)
-            finally:    # also on an exception (a prompt that does not fit): no prompt pass may outlive the call
-                if getattr(self, "_refill_stream", None) is not None:
-                    self._refill_stream.synchronize()
-
-        pred, orig = [], []
-        self.last_stats = {"slots": batch_size, "steps": 0, "kv_rows": 0, "prefill_rows": actual, "refills": 0}
-        slot_orig = first + [-1] * (batch_size - actual)
-        steps = [0] * batch_size
-        ignore = [i >= actual for i in range(batch_size)]
-        stop = False
-        idx = 0
-        since = 0
-        while not stop:
-            # the reference tests after steps 1, 6, 11, ... of each 1000-iteration inner loop
-            n = 1 if idx == 0 else check_interval
-            n = min(n, 1000 - idx) if idx else 1
-            self._decode(batch_size, n)
-            for b in range(batch_size):
-                steps[b] += n
-            self.last_stats["steps"] += n
-            since += n
-            idx += n
-            last = idx - 1
-            if idx >= 1000:
-                idx = 0
-            if last % check_interval != 0:
-                continue
-            self._flush(batch_size)
-            kv = rt["kv_len"].clone()
-            samples = rt["pre_tokens"][rows, kv.clamp(max=rt["T"])]
-            kv_h, smp = torch.stack([kv, samples.to(kv.dtype)]).tolist()   # one device->host copy per window
-            self.last_stats["kv_rows"] += sum(kv_h) * since       # ~ K/V rows read by the steps since the previous window
-            since = 0
-            cap = caps[min(bucket_i, len(caps) - 1)]
-            reached = [k + check_interval >= cap for k in kv_h]
-            eos = [t == self.EOS for t in smp]
-            if max_new_tokens is not None:   # a token budget ends a request like an EOS would
-                eos = [e or (slot_orig[b] >= 0 and steps[b] - 1 >= max_new_tokens[slot_orig[b]]) for b, e in enumerate(eos)]
-            fin = [(not ignore[b]) and (eos[b] or reached[b]) for b in range(batch_size)]
-            if not any(fin):
-                continue
-            if any(reached):
-                bucket_i += 1
-                if bucket_i < len(caps):
-                    reached = [False] * batch_size
-            fin = [(not ignore[b]) and (eos[b] or reached[b]) for b in range(batch_size)]
-            if not any(fin):
-                continue
-            refill = []   # (slot, request) pairs of this window: the reference prefills them one by one in this order
-            fin_idx = [b for b in range(batch_size) if fin[b]]
-            fin_rows = rt["pre_tokens"][fin_idx].cpu().numpy()      # one copy for every sequence that finished
-            for j, i in enumerate(fin_idx):
-                a0, b0 = kv_h[i] - steps[i] + 1, kv_h[i]
-                hit = np.nonzero(fin_rows[j, a0:b0] == self.EOS)[0]   # cut at the first EOS (t2s_model.py:675-678)
-                n_keep = int(hit[0]) if hit.size else max(0, b0 - a0)
-                if max_new_tokens is not None:
-                    n_keep = min(n_keep, int(max_new_tokens[slot_orig[i]]))
-                seg = rt["pre_tokens"][i, a0: a0 + n_keep]
-                pred.append(seg.clone())
-                orig.append(slot_orig[i])
-                if on_finish is not None:
-                    on_finish(slot_orig[i], pred[-1])
-                steps[i] = 0
-                kv_h[i] = 0
-                rt["kv_len"][i] = 0
-                mx = max(kv_h)
-                bucket_i = len(caps) - 1
-                for j, c in enumerate(caps):
-                    if c >= mx + check_interval:
-                        bucket_i = j
-                        break
-                cur = None if exhausted else nxt()
-                if cur is None:
-                    exhausted = True
-                    ignore[i] = True
-                    rt["kv_len"][i] = -1       # parked (gsv_tts_hip.h): an idle slot's steps attend over one row, not a growing cache
-                    if all(ignore):
-                        stop = True
-                        break
-                else:
-                    n_new = int(x[cur].shape[0]) + int(y[cur].shape[0])
-                    if n_new > caps[-1]:
-                        raise ValueError("prompt longer than the largest KV bucket")
-                    refill.append((i, cur))
-                    kv_h[i] = n_new            # what the slot holds once refilled: the next slots' bucket choice sees it
-                    slot_orig[i] = cur
-            if refill and not stop:
-                # rows are independent through the prefill, so the window's refills run as ONE packed prefill into their
-                # scattered slots (gsv_t2s_prefill_slots) instead of one 170-launch chain per sequence
-                req = [c for _, c in refill]
-                xy1, xl1, yl1, _, _ = self.embed_prompt([x[c] for c in req], [y[c] for c in req], [bert_feature[c] for c in req])
-                self._put_request(batch_size, [i for i, _ in refill], req, self._seed_tokens(req, y))
-                self.prefill_slots(batch_size, [i for i, _ in refill], xy1, xl1, yl1)
-                self.last_stats["refills"] += len(refill)
-                if mode == 2:
-                    rt["tok_override"][torch.tensor([i for i, _ in refill], device=dev)] = \
-                        torch.tensor([self._stream_id(c) for _, c in refill], dtype=torch.int64, device=dev)
-        return pred, torch.tensor(orig, device=dev)
+        if not async_refill:
+            return SL.reference_order(self, x, y, bert_feature, batch_size, first, nxt, exhausted, bucket_i, check_interval,
+                                      on_finish, max_new_tokens, mode)
+        try:
+            loop = SL.AheadLoop if self.refill_ahead > 0 else SL.StagedLoop
+            pred, orig = loop(self, x, y, bert_feature, batch_size, first, nxt, exhausted,
+                              [int(a) + int(b) for a, b in zip(x_lens_h, y_lens_h)], check_interval, on_finish, max_new_tokens,
+                              mode == 2).run()
+            return pred, torch.tensor(orig, device=dev)
+        finally:    # also on an exception (a prompt that does not fit): no prompt pass may outlive the call
+            if self._refill_stream is not None:
+                self._refill_stream.synchronize()
