@@ -2,11 +2,13 @@
 // CN-HuBERT (gsv_hubert_*; kernels in hubert.h, which shares refaudio.h's fgemm) and of ERes2NetV2 with its resampler and
 // fbank (gsv_sv_*; kernels in sv.h, which uses the same fgemm for the DFT and the mel filter bank) and of Chinese RoBERTa
 // (gsv_roberta_*; kernels in roberta.h, which reuses hubert.h's LayerNorm and fgemm's tile body), and the WAV sample
-// conversion in front of them all (gsv_wav_*; kernel in wavpcm.h).
+// conversion in front of them all (gsv_wav_*; kernel in wavpcm.h) with the FLAC frame decode that feeds it (gsv_flac_*;
+// flacdec.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <map>
 #include <string>
@@ -19,6 +21,7 @@
 #include "roberta.h"
 #include "sv.h"
 #include "wavpcm.h"
+#include "flacdec.h"
 
 using namespace gsv;
 
@@ -1548,6 +1551,148 @@ int gsv_wav_to_mono(const void* pcm, size_t pcm_bytes, int n_frames, int format,
     c.format = (int16_t)format;
     c.channels = (int16_t)channels;
     return gsv_wav_to_mono_batch(pcm, pcm_bytes, &c, 1, out, stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------
+// FLAC frames -> s32 staging -> fp32 mono (flacdec.h, then wavpcm.h's WAV_S32)
+// ------------------------------------------------------------------------------------------------------------------
+static_assert(FLAC_E_OVERRUN == GSV_FLAC_OVERRUN && FLAC_E_SYNC == GSV_FLAC_SYNC && FLAC_E_RESERVED == GSV_FLAC_RESERVED &&
+              FLAC_E_CRC8 == GSV_FLAC_CRC8 && FLAC_E_MISMATCH == GSV_FLAC_MISMATCH && FLAC_E_ORDER == GSV_FLAC_ORDER &&
+              FLAC_E_PARTITION == GSV_FLAC_PARTITION && FLAC_E_RESIDUAL == GSV_FLAC_RESIDUAL && FLAC_E_RANGE == GSV_FLAC_RANGE &&
+              FLAC_E_LENGTH == GSV_FLAC_LENGTH && FLAC_E_CRC16 == GSV_FLAC_CRC16 && FLAC_E_WASTED == GSV_FLAC_WASTED,
+              "flacdec.h's status codes are the ABI's GSV_FLAC_* codes");
+static_assert(sizeof(FlacFrameDev) == 32, "device frame table entry");
+
+namespace {
+
+constexpr size_t kFlacAlign = 256;
+constexpr int kFlacWaveSlots = 1024;    // 256 CUs x 4 SIMDs: below this many frames each wave decodes one frame
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+size_t flac_table_bytes(int n_frames) { return align_up((size_t)n_frames * sizeof(FlacFrameDev), kFlacAlign); }
+
+// the argument checks of gsv_flac_decode / gsv_flac_decode_host; base[c]: clip c's first s32 in the interleaved
+// staging (clips back to back), total: its length
+int flac_check(const void* bytes, size_t n_bytes, const gsv_flac_clip* clips, int n_clips, const gsv_flac_frame* frames,
+               int n_frames, long long* base, long long* total) {
+    if (!bytes || !clips || !frames) return abi_fail(GSV_ERR_ARG, "null argument");
+    if (n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS) return abi_fail(GSV_ERR_ARG, "flac: %d clips (1..%d per call)", n_clips, GSV_AUX_MAX_CLIPS);
+    if (n_frames < 1) return abi_fail(GSV_ERR_ARG, "flac: %d frames", n_frames);
+    long long next[GSV_AUX_MAX_CLIPS], at = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        const gsv_flac_clip& k = clips[c];
+        if (k.channels < 1 || k.channels > 2) return abi_fail(GSV_ERR_ARG, "flac: clip %d: %d channels (1 or 2)", c, k.channels);
+        if (k.bits_per_sample < 8 || k.bits_per_sample > 24)
+            return abi_fail(GSV_ERR_ARG, "flac: clip %d: %d bits per sample (8..24)", c, k.bits_per_sample);
+        if (k.n_samples < 1) return abi_fail(GSV_ERR_ARG, "flac: clip %d: %d samples", c, k.n_samples);
+        if (k.out_offset < 0) return abi_fail(GSV_ERR_ARG, "flac: clip %d: out_offset %lld", c, (long long)k.out_offset);
+        base[c] = at;
+        at += (long long)k.n_samples * k.channels;
+        next[c] = 0;
+    }
+    *total = at;
+    for (int f = 0; f < n_frames; ++f) {
+        const gsv_flac_frame& r = frames[f];
+        if (r.clip < 0 || r.clip >= n_clips) return abi_fail(GSV_ERR_ARG, "flac: frame %d: clip %d of %d", f, r.clip, n_clips);
+        if (r.block_size < 1 || r.block_size > 65535) return abi_fail(GSV_ERR_ARG, "flac: frame %d: block size %d", f, r.block_size);
+        if (r.byte_offset < 0 || r.byte_len < 1 || (unsigned long long)r.byte_offset > n_bytes ||
+            (unsigned long long)r.byte_len > n_bytes - (unsigned long long)r.byte_offset)
+            return abi_fail(GSV_ERR_ARG, "flac: frame %d: %d bytes at byte %lld run past the %zu bytes given", f, r.byte_len,
+                            (long long)r.byte_offset, n_bytes);
+        if (r.first_sample != next[r.clip])
+            return abi_fail(GSV_ERR_ARG, "flac: frame %d: starts at sample %d of clip %d where sample %lld is next (frames of a clip "
+                            "come in order and tile it)", f, r.first_sample, r.clip, next[r.clip]);
+        next[r.clip] += r.block_size;
+        if (next[r.clip] > clips[r.clip].n_samples)
+            return abi_fail(GSV_ERR_ARG, "flac: frame %d: ends at sample %lld of clip %d, which has %d", f, next[r.clip], r.clip,
+                            clips[r.clip].n_samples);
+    }
+    for (int c = 0; c < n_clips; ++c)
+        if (next[c] != clips[c].n_samples)
+            return abi_fail(GSV_ERR_ARG, "flac: clip %d: its frames hold %lld of %d samples", c, next[c], clips[c].n_samples);
+    return GSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gsv_flac_decode_workspace(const gsv_flac_clip* clips, int n_clips, int n_frames) {
+    if (!clips || n_clips < 1 || n_clips > GSV_AUX_MAX_CLIPS || n_frames < 1) return 0;
+    size_t s32 = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        if (clips[c].n_samples < 1 || clips[c].channels < 1 || clips[c].channels > 2) return 0;
+        s32 += (size_t)clips[c].n_samples * clips[c].channels;
+    }
+    return flac_table_bytes(n_frames) + align_up(s32 * sizeof(int32_t), kFlacAlign);
+}
+
+int gsv_flac_decode(const void* bytes_dev, size_t n_bytes, const gsv_flac_clip* clips, int n_clips, const gsv_flac_frame* frames,
+                    int n_frames, float* out, int32_t* status_dev, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!out || !status_dev || !workspace) return abi_fail(GSV_ERR_ARG, "null argument");
+    long long base[GSV_AUX_MAX_CLIPS], total = 0;
+    int rc;
+    if ((rc = flac_check(bytes_dev, n_bytes, clips, n_clips, frames, n_frames, base, &total))) return rc;
+    const size_t need = gsv_flac_decode_workspace(clips, n_clips, n_frames);
+    if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return abi_fail(GSV_ERR_ARG, "flac: workspace of %zu bytes (%zu needed, 16-byte aligned)", workspace_bytes, need);
+    hipStream_t st = S(stream);
+    FlacFrameDev* tab_dev = static_cast<FlacFrameDev*>(workspace);
+    int32_t* staging = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + flac_table_bytes(n_frames));
+    std::vector<FlacFrameDev> tab((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        const gsv_flac_frame& r = frames[f];
+        const gsv_flac_clip& k = clips[r.clip];
+        FlacFrameDev& d = tab[f];
+        d.byte_off = r.byte_offset;
+        d.out_off = base[r.clip] + (long long)r.first_sample * k.channels;
+        d.byte_len = (unsigned)r.byte_len;
+        d.block_size = r.block_size;
+        d.channels = (short)k.channels;
+        d.bps = (short)k.bits_per_sample;
+        d.open_end = r.flags & GSV_FLAC_OPEN_END;
+    }
+    // pageable host memory: the copy has left `tab` when the call returns
+    RCHK(hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(FlacFrameDev), hipMemcpyHostToDevice, st));
+    const int fpb = std::min(64, std::max(1, cdiv(n_frames, kFlacWaveSlots)));
+    flac_frames_kernel<<<dim3((unsigned)cdiv(n_frames, fpb)), 64, 0, st>>>(static_cast<const unsigned char*>(bytes_dev), tab_dev,
+                                                                          n_frames, fpb, staging, status_dev);
+    RCHK(hipGetLastError());
+    WavClips cl;
+    int n_max = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        cl.off[c] = base[c] * (long long)sizeof(int32_t);
+        cl.out0[c] = clips[c].out_offset;
+        cl.n[c] = clips[c].n_samples;
+        cl.fmt[c] = WAV_S32;
+        cl.ch[c] = (short)clips[c].channels;
+        n_max = std::max(n_max, (int)clips[c].n_samples);
+    }
+    wav_to_mono_kernel<<<dim3((unsigned)((n_max + 255) / 256), n_clips), 256, 0, st>>>(
+        reinterpret_cast<const unsigned char*>(staging), cl, out);
+    RCHK(hipGetLastError());
+    return GSV_OK;
+}
+
+int gsv_flac_decode_host(const void* bytes, size_t n_bytes, const gsv_flac_clip* clips, int n_clips, const gsv_flac_frame* frames,
+                         int n_frames, int32_t* pcm_interleaved, int32_t* status) {
+    if (!pcm_interleaved || !status) return abi_fail(GSV_ERR_ARG, "null argument");
+    long long base[GSV_AUX_MAX_CLIPS], total = 0;
+    int rc;
+    if ((rc = flac_check(bytes, n_bytes, clips, n_clips, frames, n_frames, base, &total))) return rc;
+    for (int f = 0; f < n_frames; ++f) {
+        const gsv_flac_frame& r = frames[f];
+        const gsv_flac_clip& k = clips[r.clip];
+        status[f] = flac_decode_frame(static_cast<const unsigned char*>(bytes) + r.byte_offset, (uint32_t)r.byte_len, k.channels,
+                                      k.bits_per_sample, r.block_size,
+                                      pcm_interleaved + base[r.clip] + (long long)r.first_sample * k.channels, 0,
+                                      (r.flags & GSV_FLAC_OPEN_END) != 0);
+    }
+    return GSV_OK;
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ EXPORTS = [
     "gsv_roberta_create", "gsv_roberta_destroy", "gsv_roberta_load_tensor", "gsv_roberta_finalize", "gsv_roberta_workspace",
     "gsv_roberta_forward", "gsv_roberta_features",
     "gsv_wav_to_mono", "gsv_wav_to_mono_batch",
+    "gsv_flac_decode_workspace", "gsv_flac_decode", "gsv_flac_decode_host",
 ]
 
 
@@ -97,6 +98,30 @@ class WavClip(ctypes.Structure):
     _fields_ = [("byte_offset", ctypes.c_int64), ("n_frames", ctypes.c_int32), ("format", ctypes.c_int16),
                 ("channels", ctypes.c_int16)]
 
+
+class FlacClip(ctypes.Structure):
+    """gsv_flac_clip: one clip of gsv_flac_decode"""
+    _fields_ = [("channels", ctypes.c_int32), ("bits_per_sample", ctypes.c_int32), ("n_samples", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("out_offset", ctypes.c_int64)]
+
+
+class FlacFrame(ctypes.Structure):
+    """gsv_flac_frame: one frame of gsv_flac_decode"""
+    _fields_ = [("clip", ctypes.c_int32), ("block_size", ctypes.c_int32), ("byte_offset", ctypes.c_int64),
+                ("byte_len", ctypes.c_int32), ("first_sample", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+FLAC_OPEN_END = 1       # GSV_FLAC_OPEN_END
+
+
+# GSV_FLAC_*: what a frame's status says
+FLAC_STATUS = ("ok", "overrun: the frame's structure needs more bits than the frame holds", "no frame sync code",
+               "a reserved code", "header CRC-8 mismatch", "header disagrees with STREAMINFO or the frame index",
+               "predictor order larger than the block", "residual partitions do not divide the block",
+               "residual outside 32 bits", "sample outside the stream's bits per sample",
+               "the frame's structure ends before its last bytes", "CRC-16 mismatch", "wasted bits leave no bit of the sample")
+FLAC_CRC16 = 11
 
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = range(6)   # GSV_PCM_*
 
@@ -196,6 +221,8 @@ def lib():
         "gsv_roberta_features": [vp, vp, vp, i, i, i, vp, i, vp, vp, sz, vp],
         "gsv_wav_to_mono": [vp, sz, i, i, i, vp, vp],
         "gsv_wav_to_mono_batch": [vp, sz, ctypes.POINTER(WavClip), i, vp, vp],
+        "gsv_flac_decode": [vp, sz, ctypes.POINTER(FlacClip), i, ctypes.POINTER(FlacFrame), i, vp, vp, vp, sz, vp],
+        "gsv_flac_decode_host": [vp, sz, ctypes.POINTER(FlacClip), i, ctypes.POINTER(FlacFrame), i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -227,6 +254,8 @@ def lib():
     L.gsv_sv_batch_workspace.restype = sz
     L.gsv_roberta_workspace.argtypes = [vp, i, i, i]
     L.gsv_roberta_workspace.restype = sz
+    L.gsv_flac_decode_workspace.argtypes = [ctypes.POINTER(FlacClip), i, i]
+    L.gsv_flac_decode_workspace.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

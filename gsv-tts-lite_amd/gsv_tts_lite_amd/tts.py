@@ -18,9 +18,10 @@ holds a CJK ideograph (the reference asks LangSegment for "zh", which is not ava
 text loads it too).  Either sets tts_config.cnroberta, so a frontend written as
 `lambda t: get_phones_and_bert(t, tts.tts_config)` gets device BERT features; without the directory one warning is
 logged and bert2 stays zeros.  Reference audio given as a path that names an existing WAV file (PCM or IEEE float, mono
-or stereo) is read as TTS._load_audio reads it: the container parsed on the host, the samples converted to fp32 mono on
-the device (wavio.py), so infer("spk.wav", "prompt.wav", ...) works as in the reference.  What else sits in front of the
-hot path in the reference -- G2P text frontends and decoding compressed audio (mp3, ogg, flac) -- is OUT OF SCOPE of this
+or stereo) or FLAC file (8..24 bits, mono or stereo) is read as TTS._load_audio reads it: the container parsed on the
+host, the samples converted to fp32 mono on the device (wavio.py) -- FLAC frames decoded there first (flacio.py) -- so
+infer("spk.wav", "prompt.flac", ...) works as in the reference.  What else sits in front of the
+hot path in the reference -- G2P text frontends and decoding lossy compressed audio (mp3, ogg) -- is OUT OF SCOPE of this
 build (CPU string processing and third-party packages not installable here).  Their
 *outputs* enter through the same caches the reference keeps:
     cache_spk_audio(path)  or  cache_spk_audio(path, ge=...)  or
@@ -252,7 +253,7 @@ class TTS:
     def cache_spk_audio(self, spk_audio_paths, sovits_model=None, ge=None, audio=None, sv_emb=None, sample_rate=None):
         """TTS.py:1346-1389.  Either the finished embedding `ge` [1, gin, 1], or the reference waveform `audio`
         (mono fp32 at `sample_rate`, None: the model rate; resampled to the model rate on the device, what TTS._load_audio
-        + _resample give), or neither when the key names an existing WAV file, which is then read (wavio.load_wav) and
+        + _resample give), or neither when the key names an existing WAV or FLAC file, which is then read (wavio.load_wav, flacio.load_flac) and
         resampled to the model rate: then the spectrogram (TTS._get_spec) and get_ge run on the device.  v2Pro / v2ProPlus add the ERes2Net embedding sv_emb [1, 20480]: the one passed, else the
         one this path's cache entry holds, else ERes2NetV2 on the device (16 kHz resample + fbank + forward3) from
         models_dir/sv/pretrained_eres2netv2w24s4ep4.ckpt, kept loaded only when always_load_sv is set.  Without that
@@ -261,7 +262,7 @@ class TTS:
         A list of keys caches many speakers in one call (what the reference's cache_spk_audio(*paths) does): `audio` a list
         with one waveform per key, `ge` / `sv_emb` None or lists of the same length (None entries allowed).  ERes2NetV2 is
         loaded once and runs every clip that needs an sv_emb in one batched pass; each entry equals what a single-key call
-        gives; `sample_rate` is then one rate for all or a list, and keys with neither audio nor ge that name WAV files
+        gives; `sample_rate` is then one rate for all or a list, and keys with neither audio nor ge that name WAV or FLAC files
         are read in one packed pass (wavio.load_wavs).  Any other key (a str, a tuple) is one key, as before."""
         if isinstance(spk_audio_paths, list):
             return self._cache_spk_batch(spk_audio_paths, sovits_model, ge, audio, sv_emb, sample_rate)
@@ -274,8 +275,7 @@ class TTS:
                     raise NotImplementedError("%r is no existing WAV file, and decoding / resampling audio files is outside "
                                               "this build's scope; pass ge=[1, gin, 1], or audio=<waveform> (+ sv_emb=[1, "
                                               "20480])" % (spk_audio_paths,))
-                from .wavio import load_wav
-                audio, sample_rate = load_wav(path, self.tts_config.device)
+                audio, sample_rate = self._read_files([path])[0]
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
             sovits = self.sovits_models[sovits_model]
@@ -324,8 +324,7 @@ class TTS:
         todo = [i for i in range(n) if ges[i] is None]
         if todo:
             if files:
-                from .wavio import load_wavs
-                for i, (w, sr) in zip(files, load_wavs(list(files.values()), self.tts_config.device)):
+                for i, (w, sr) in zip(files, self._read_files(list(files.values()))):
                     auds[i], rates[i] = w, sr
             if sovits_model not in self.sovits_models:
                 self.load_sovits_model(sovits_model)
@@ -359,6 +358,26 @@ class TTS:
     def _wav_file(key):
         """key when it is a path (str or os.PathLike) naming an existing file, read as WAV; None for any other key"""
         return key if isinstance(key, (str, os.PathLike)) and os.path.isfile(key) else None
+
+    def _read_files(self, paths):
+        """TTS._load_audio of existing files -> [(fp32 mono on the device, the file's rate)], each at its own path's
+        index.  A file that starts with the FLAC marker goes to flacio (frames decoded on the device), every other one
+        to wavio as before (which names what it cannot read); all WAV files are read in one load_wavs and all FLAC files
+        in one load_flacs, whatever order they come in."""
+        from .flacio import load_flacs
+        from .wavio import load_wavs
+        flac = []
+        for i, p in enumerate(paths):
+            with open(p, "rb") as f:
+                if f.read(4) == b"fLaC":
+                    flac.append(i)
+        wav = [i for i in range(len(paths)) if i not in set(flac)]
+        res = [None] * len(paths)
+        for idx, load in ((wav, load_wavs), (flac, load_flacs)):
+            if idx:
+                for i, r in zip(idx, load([paths[i] for i in idx], self.tts_config.device)):
+                    res[i] = r
+        return res
 
     def _spk_wave(self, audio, sample_rate, rate):
         """TTS._get_spec's waveform: audio at sample_rate (None: already at `rate`) -> fp32 [1, n] on the device at the
@@ -403,7 +422,7 @@ class TTS:
 
     def verify_speaker(self, speaker1_audio, speaker2_audio) -> float:
         """TTS.py:1205-1245: cosine similarity (eps 1e-6) of two speakers' ERes2NetV2 embeddings.  Each argument is a
-        cache_spk_audio key whose entry holds an sv_emb, a path that is no cached key and names an existing WAV file (read
+        cache_spk_audio key whose entry holds an sv_emb, a path that is no cached key and names an existing WAV or FLAC file (read
         and resampled to the model rate as cache_spk_audio does; nothing is cached), or a mono fp32 waveform at the model
         rate (that of the first loaded SoVITS model, 32 kHz when none is loaded), peak-normalised here as TTS._get_spec
         does."""
@@ -413,8 +432,7 @@ class TTS:
             if isinstance(a, (str, Path)):
                 path = None if a in self.spk_audio_cache else self._wav_file(a)
                 if path is not None:
-                    from .wavio import load_wav
-                    return self._sv_embed(self._spk_wave(*load_wav(path, self.tts_config.device), rate), rate)
+                    return self._sv_embed(self._spk_wave(*self._read_files([path])[0], rate), rate)
                 e = self.spk_audio_cache.get(a, {}).get("sv_emb")
                 if e is None:
                     raise NotImplementedError("decoding / resampling audio files is outside this build's scope; cache %r "
@@ -434,14 +452,14 @@ class TTS:
         CN-HuBERT (TTS._get_prompt: + 0.3 s of zeros) and extract_latent run on the device.  CN-HuBERT is loaded from
         models_dir/chinese-hubert-base on first use and kept only when always_load_cnhubert is set.  Audio at another
         `sample_rate` is first resampled to 16 kHz on the device (torchaudio Resample defaults, sv.resample).  With none of
-        prompt / ssl_content / audio, a key that names an existing WAV file is read (wavio.load_wav) and takes that path at
+        prompt / ssl_content / audio, a key that names an existing WAV or FLAC file is read (wavio.load_wav, flacio.load_flac) and takes that path at
         the file's rate; phones1 (and bert1) then come from the text frontend when not given, as the reference's
         get_phones_and_bert(prompt_audio_text) (TTS.py:1424).
 
         A list of keys caches many prompts in one call (the reference's list form): `audio` a list with one waveform per
         key, `prompt_audio_texts` one str for all or a list, `phones1` one list[int] for all or a list of them, `bert1`
         None or a list, `sample_rate` one int or a list.  A key whose audio is None (or every key, without audio) that
-        names an existing WAV file is read, all such files in one packed pass; when every key is read from a file,
+        names an existing WAV or FLAC file is read, all such files in one packed pass; when every key is read from a file,
         phones1 may be left out and comes from the text frontend.  CN-HuBERT is loaded once and runs every clip in one
         batched pass, then extract_latent runs per clip; each entry equals what a single-key call gives.  Lengths and
         empty texts are checked before any device work.  Any other key (a str, a tuple) is one key, as before."""
@@ -455,8 +473,7 @@ class TTS:
             if phones1 is None and self._text_frontend is not None:      # TTS.py:1424
                 phones1, _, fb, _ = self._phones_and_bert(prompt_audio_texts)
                 bert1 = fb if bert1 is None else bert1
-            from .wavio import load_wav
-            audio, sample_rate = load_wav(path, self.tts_config.device)
+            audio, sample_rate = self._read_files([path])[0]
         if prompt is None and ssl_content is None and audio is not None:
             if int(sample_rate) != 16000:
                 from .sv import resample
@@ -527,8 +544,7 @@ class TTS:
             berts = [f[2] if b is None else b for f, b in zip(fronts, berts)]
         rates = self._per_key(sample_rate, n, "sample_rate", lambda v: isinstance(v, numbers.Integral))
         if files:
-            from .wavio import load_wavs
-            for i, (w, sr) in zip(files, load_wavs(list(files.values()), self.tts_config.device)):
+            for i, (w, sr) in zip(files, self._read_files(list(files.values()))):
                 auds[i], rates[i] = w, sr
         wavs = []
         for i, a in enumerate(auds):

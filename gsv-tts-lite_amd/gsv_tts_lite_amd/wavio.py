@@ -8,7 +8,9 @@ device (gsv_wav_to_mono*, csrc/wavpcm.h).
 Only the data chunk's bytes cross to the device, as they are in the file.  Read: format tags 1 (integer PCM: u8, s16,
 packed s24, s32), 3 (IEEE float: f32, f64) and 0xFFFE (WAVE_FORMAT_EXTENSIBLE with the PCM or float sub-format), one or
 two channels.  Compressed audio (MP3, Ogg, FLAC, A-law, mu-law, ADPCM) and more than two channels raise
-NotImplementedError: they need a decoder, or ffmpeg's downmix matrices, outside this build.  No CPU path."""
+NotImplementedError here: they need a decoder, or ffmpeg's downmix matrices, outside this module.  (Native FLAC files
+have their own reader beside this one, flacio.py, and the facade sends a file that starts with "fLaC" there; this module
+stays WAV-only.)  No CPU path."""
 import struct
 from collections import namedtuple
 

@@ -546,6 +546,59 @@ typedef struct gsv_wav_clip {
 /* up to GSV_AUX_MAX_CLIPS clips (a HOST array) in one launch: out holds clip i's [n_frames_i] at offset
  * sum_{j<i} n_frames_j, bit-identical to gsv_wav_to_mono on that clip.  GSV_ERR_ARG names the first bad clip. */
 int gsv_wav_to_mono_batch(const void* pcm, size_t pcm_bytes, const gsv_wav_clip* clips, int n_clips, float* out, void* stream);
+/* Reference-audio files, FLAC: the frames of up to GSV_AUX_MAX_CLIPS files, packed into one device byte buffer, decoded
+ * on the device (csrc/flacdec.h: one lane per frame) into interleaved s32 staging, left-justified, which the WAV path's
+ * own conversion (GSV_PCM_S32) then turns into fp32 mono: a FLAC clip is bit-identical to the WAV file holding the same
+ * integers.  1 or 2 channels, 8..24 bits per sample.  The host parses the container and indexes the frames
+ * (gsv_tts_lite_amd/flacio.py); the tables below are HOST arrays, read before the call returns. */
+typedef struct gsv_flac_clip {
+    int32_t channels;          /* 1 or 2 */
+    int32_t bits_per_sample;   /* 8..24, from STREAMINFO */
+    int32_t n_samples;         /* per channel */
+    int32_t reserved;
+    int64_t out_offset;        /* of the clip's fp32 mono samples in `out`, in samples */
+} gsv_flac_clip;
+typedef struct gsv_flac_frame {
+    int32_t clip;              /* index into the clip table */
+    int32_t block_size;        /* samples per channel in this frame, 1..65535 */
+    int64_t byte_offset;       /* of the frame's sync code in the packed bytes */
+    int32_t byte_len;          /* through its CRC-16; with GSV_FLAC_OPEN_END an upper bound */
+    int32_t first_sample;      /* within the clip */
+    int32_t flags;             /* GSV_FLAC_OPEN_END or 0 */
+    int32_t reserved;
+} gsv_flac_frame;
+/* a file's last frame: no header follows it, so the host cannot know where it ends (bytes may trail it).  The decoder
+ * then reads the CRC-16 from where the frame's structure ends, anywhere inside byte_len. */
+#define GSV_FLAC_OPEN_END 1
+/* status codes a frame can end with (status[i] of frame i; a failed frame's samples are zero) */
+#define GSV_FLAC_OK 0
+#define GSV_FLAC_OVERRUN 1      /* the frame's structure needs more bits than byte_len holds */
+#define GSV_FLAC_SYNC 2         /* no sync code, or a reserved header bit */
+#define GSV_FLAC_RESERVED 3     /* a reserved code */
+#define GSV_FLAC_CRC8 4         /* header CRC-8 mismatch */
+#define GSV_FLAC_MISMATCH 5     /* header disagrees with the tables (block size, channels, bits per sample) */
+#define GSV_FLAC_ORDER 6        /* predictor order larger than the block */
+#define GSV_FLAC_PARTITION 7    /* residual partitions do not divide the block */
+#define GSV_FLAC_RESIDUAL 8     /* residual outside 32 bits */
+#define GSV_FLAC_RANGE 9        /* sample outside the stream's bits per sample */
+#define GSV_FLAC_LENGTH 10      /* the structure ends before byte_len - 2 */
+#define GSV_FLAC_CRC16 11       /* frame CRC-16 mismatch */
+#define GSV_FLAC_WASTED 12      /* wasted bits leave no bit of the sample */
+/* device bytes of the workspace of gsv_flac_decode (the device frame table + the s32 staging); 0 on bad arguments */
+size_t gsv_flac_decode_workspace(const gsv_flac_clip* clips, int n_clips, int n_frames);
+/* bytes: n_bytes DEVICE bytes; out: fp32, clip c at out_offset_c .. + n_samples_c; status_dev: int32 [n_frames] on the
+ * device.  Checked before anything is launched, each GSV_ERR_ARG with gsv_last_error naming the first bad entry: 1..
+ * GSV_AUX_MAX_CLIPS clips, channels 1 or 2, bits 8..24, every frame inside n_bytes, the frames of each clip (in table
+ * order) tiling [0, n_samples) exactly, the workspace large enough and 16-byte aligned.  One table upload and two
+ * launches (frames, mono conversion) on `stream`; nothing is allocated. */
+int gsv_flac_decode(const void* bytes_dev, size_t n_bytes, const gsv_flac_clip* clips, int n_clips,
+                    const gsv_flac_frame* frames, int n_frames, float* out, int32_t* status_dev, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The same frame routine run by the CPU over HOST memory, for tests and tools (not an inference path): the integers as
+ * they were encoded (right-justified), interleaved, clip c at sum_{j<c} n_samples_j * channels_j of pcm_interleaved;
+ * status: int32 [n_frames].  The same argument checks; out_offset is not used.  Needs no GPU. */
+int gsv_flac_decode_host(const void* bytes, size_t n_bytes, const gsv_flac_clip* clips, int n_clips,
+                         const gsv_flac_frame* frames, int n_frames, int32_t* pcm_interleaved, int32_t* status);
 /* fbank frames of a waveform of n_samples at sample_rate once it is at 16 kHz: 1 + (n16 - 400) / 160, 0 if n16 < 400 */
 int gsv_sv_frames(gsv_sv* h, int n_samples, int sample_rate);
 /* device bytes of the caller-owned workspace of gsv_sv_embed over n_samples at sample_rate; it also covers
