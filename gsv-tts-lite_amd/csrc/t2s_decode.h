@@ -58,10 +58,23 @@ __device__ __forceinline__ void eos_publish(int32_t* eos_host, int slot, int val
 //
 // Latency discipline.  The step is a chain of ~50 dependent kernels and, at batch 1, each kernel
 // runs on a handful of CUs, so what matters is the length of the dependent chain inside a kernel:
-//  * every global load whose ADDRESS does not depend on this kernel's activations -- partial sums,
-//    weight rows, K/V rows, out-proj panel, biases -- is issued at kernel entry into registers, in
-//    the order it will be consumed (loads retire in order), and an opaque asm pins "all loads
+//  * the loads that the kernel's FIRST phases consume -- partial sums, their bias / residual / LayerNorm
+//    rows, the weight rows of the first GEMV and its bias -- are issued at kernel entry into registers,
+//    in the order they will be consumed (loads retire in order), and an opaque asm pins "these loads
 //    issued, then arithmetic" (hipcc otherwise sinks the loads next to their first use);
+//  * what is needed LATER is issued later, although its address is known at entry too: the first
+//    chunk's K/V rows behind the partial-sum barrier, by the attention waves, which on bf16 handles are
+//    the eight waves that own no LayerNorm element and only meet its barriers; the out-proj panel behind
+//    the QKV dots; the FFN's W2 panel behind the partial-sum barrier.  A CU takes about one 1-KiB wave
+//    load per 16 cycles, and a wave reaches its park() only once it has ISSUED every load in front of it:
+//    with everything at entry the last wave of a bf16 attention block was still issuing 5.75k cycles in
+//    (its own partial rows long landed), and the partial-sum barrier and the LayerNorm wait for the last
+//    wave.  The deferred loads take issue slots while their wave would wait at a barrier anyway, and
+//    still land ahead of their use (profiles/decode_load_staging.txt: last wave past the pin at 3.9k
+//    cycles instead of 6.0k, the attention block 13.7k -> 12.6k, the FFN block 5.5k -> 5.3k);
+//  * hipcc counts a wait by the path with the FEWEST loads behind the awaited one (vmcnt is one in-order
+//    counter): where only some waves issue a load group (K/V), every wait behind it also covers that
+//    group on those waves.  So such a group goes where nothing issued earlier is awaited for long;
 //  * the instruction stream per wave is what the kernel's wall time is made of once the loads
 //    overlap (one wave issues ~1 VALU op per 4-5 cycles), so a block is 16 waves (1024 threads):
 //    4 waves per SIMD share the rows/keys, each wave's stream is a quarter of a 256-thread block's.
@@ -484,9 +497,14 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     // thread issue a quarter fewer instructions than sixteen with two (bf16: 0.2735 -> 0.2695 ms per step at one sequence, 0.297 -> 0.288 at 4;
     // fp32 handles keep sixteen: eight K/V vectors more per thread spill there, 0.433 -> 0.473 ms)
     constexpr int AW = sizeof(WT) == 2 ? 8 : kNW;
+    // ... and they are the LAST AW waves: on bf16 handles the eight that own no LayerNorm element.  Those only meet the LayerNorm's
+    // barriers, so they issue the K/V loads of the first chunk there while the owner waves reduce (Latency discipline, above).
+    // Everything the phase indexes by wave -- K/V rows, pacc / pm / pl, the new token's own key -- goes by the wave's attention
+    // index wid - AW0, so every sum keeps its order.
+    constexpr int AW0 = kNW - AW;          // first attention wave (8 bf16, 0 f32)
     constexpr int RPI = AW * 64 / LPR;     // K/V rows per block iteration (256 bf16, 128 f32 at 16 waves)
     constexpr int KCH = 2 * kNW / AW;      // iterations held in registers per chunk (512 positions bf16, 256 f32)
-    const bool aw = __builtin_amdgcn_readfirstlane(wid) < AW;
+    const bool aw = (unsigned)(__builtin_amdgcn_readfirstlane(wid) - AW0) < (unsigned)AW;
     constexpr int RW = 96 / kNW;           // 6 QKV rows per wave
     const bool owner = tid < kD;
     constexpr bool BF = sizeof(WT) == 2;   // bf16 handle: dots on v_dot2c_f32_bf16, activations as bf16 in LDS (see dot8)
@@ -496,15 +514,15 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     uint16_t* atth = reinterpret_cast<uint16_t*>(att);   // attention output [32] over att
     stamp(a.dbg, 0);
 
-    // kv_len is loaded FIRST and used LAST: only the K/V row addresses need it.  (Clamping right here made hipcc wait for this --
-    // cold -- load before it issued a single weight load: the whole weight stream started 1.5k cycles late.)
+    // kv_len is loaded FIRST and used behind the pin: only the K/V row addresses need it.  (Clamping right here made hipcc wait for
+    // this -- cold -- load before it issued a single weight load: the whole weight stream started 1.5k cycles late.)
     // (its LOW dword only: hipcc re-used the unused upper half of a 64-bit destination as a temporary and put the wait there)
     int kvl_raw = reinterpret_cast<const int*>(a.kv_len)[2 * b];
     WT* Kp = a.kc + (((size_t)b * kH + h) * a.T) * kDh;
     WT* Vp = a.vc + (((size_t)b * kH + h) * a.T) * kDh;
-    const int part = tid % LPR, rsub = tid / LPR;
+    const int part = tid % LPR, rsub = tid / LPR - AW0 * 64 / LPR;   // K/V rows go by the attention index
 
-    // ---- issue everything whose address is known now, in consumption order
+    // ---- at entry: what the layer input and the QKV dots consume, in consumption order
     PartialSum<NJ, typename Geo<WT>::PT> ps;
     float xd = 0.f;
     StepTokLoads tl;
@@ -524,37 +542,42 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     raw16 wq[RW][CPR];
 #pragma unroll
     for (int r = 0; r < RW; ++r) row_load<WT, NT>(wp + (size_t)r * kD, wq[r]);
-    Panel<WT, kDh> po;
-    // fp32 handles: the out-proj panel (16 registers) is requested BEHIND the q / k / v rows' dots, when their 48 weight registers are
-    // free -- at kernel entry the two together spilled 11 registers (and a spilled load is a wait at the top of the kernel); the panel has
-    // the whole attention phase to land
-    if constexpr (BF) po.template issue<NT>(a.wo + (size_t)h * kD * kDh);
     const int oi = sumN_index<8>();
     const float bq = a.bqkv[h * 96 + wid * RW + min(oi, RW - 1)];
-    // ... and now kv_len (the opaque asm keeps its first use -- and with it the wait -- down here, behind the weight loads)
-    asm volatile("" : "+v"(kvl_raw) : : "memory");
+    // Pin "the entry loads issued, THEN arithmetic": the opaque asm redefines the head of the partial-sum
+    // chain, so no add can be scheduled above it, while the memory clobber keeps every load above
+    // it.  It only needs the FIRST-issued loads to have landed (kv_len among them: its first use sits here).
+    stamp(a.dbg, 7);
+    if constexpr (MODE == 0) asm volatile("" : "+v"(xd), "+v"(kvl_raw) : : "memory");
+    else if constexpr (MODE == 2) asm volatile("" : "+v"(tl.tp.v), "+v"(kvl_raw) : : "memory");
+    else asm volatile("" : "+v"(ps.p[0][0]), "+v"(kvl_raw) : : "memory");
+    stamp(a.dbg, 1);
     int n = kvl_raw;
     // kv_len < 0 = a PARKED slot (include/gsv_tts_hip.h, staged refill): its K/V row goes to the last row of the cache,
     // which no prompt pass writes, and it attends over row 0 only -- it must not touch rows a concurrent refill fills
     const int nw = n < 0 ? a.T - 1 : (n > a.T - 1 ? a.T - 1 : n);
     if (n > a.T - 1) n = a.T - 1;  // memory safety only; the host never steps a full cache
     if (n < 0) n = 0;
-    // K/V rows are loaded UNCONDITIONALLY from a clamped (always valid) row and masked at use: a
-    // per-element "load or zero" select makes hipcc branch around each load and drain vmcnt(0)
+    // The first chunk's K/V rows, DEFERRED: the attention waves request them once the partial rows are parked (MODE 1) or the layer
+    // input is on its way to LDS, not at entry, where every wave of the block would have to queue them before it could park.
+    // They are loaded UNCONDITIONALLY from a clamped (always valid) row and masked at use: a per-element "load or zero" select
+    // makes hipcc branch around each load and drain vmcnt(0).  A deferred load may run after this block's own append to row
+    // nw; a register loaded from a row >= n is never used unmasked, so what it then holds does not matter.
     raw16 kreg[KCH], vreg[KCH];
-    if (AW == kNW || aw) {
+    // (issue_k has no compiler barrier of its own: every call is followed by issue_v's or by ln512's barrier -- keep it so)
+    auto issue_k = [&]() {
+        if (AW == kNW || aw) {
 #pragma unroll
-        for (int it = 0; it < KCH; ++it) kreg[it] = ldg16w<NTKV>(Kp + (size_t)min(rsub + it * RPI, n) * kDh + part * EPL);
+            for (int it = 0; it < KCH; ++it) kreg[it] = ldg16w<NTKV>(Kp + (size_t)min(rsub + it * RPI, n) * kDh + part * EPL);
+        }
+    };
+    auto issue_v = [&]() {
+        if (AW == kNW || aw) {
 #pragma unroll
-        for (int it = 0; it < KCH; ++it) vreg[it] = ldg16w<NTKV>(Vp + (size_t)min(rsub + it * RPI, n) * kDh + part * EPL);
-    }
-    // Pin "all loads issued, THEN arithmetic": the opaque asm redefines the head of the partial-sum
-    // chain, so no add can be scheduled above it, while the memory clobber keeps every load above
-    // it.  It only needs the FIRST-issued load to have landed.
-    if constexpr (MODE == 0) asm volatile("" : "+v"(xd) : : "memory");
-    else if constexpr (MODE == 2) asm volatile("" : "+v"(tl.tp.v) : : "memory");
-    else asm volatile("" : "+v"(ps.p[0][0]) : : "memory");
-    stamp(a.dbg, 1);
+            for (int it = 0; it < KCH; ++it) vreg[it] = ldg16w<NTKV>(Vp + (size_t)min(rsub + it * RPI, n) * kDh + part * EPL);
+        }
+        asm volatile("" : : : "memory");
+    };
 
     // ---- layer input
     float v;
@@ -565,7 +588,17 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     } else {
         ps.park(stage);
         __syncthreads();
+        // attention waves that own no LayerNorm element (bf16) request K and V here and then only meet the barriers; where every wave
+        // is both (fp32), V waits behind the LayerNorm's barrier so that the owners' statistics do not queue behind it
+        issue_k();
+        if constexpr (AW0 > 0) issue_v();
         v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
+        if constexpr (AW0 == 0) issue_v();
+    }
+    if constexpr (MODE != 1) {
+        asm volatile("" : "+v"(v) : : "memory");
+        issue_k();
+        issue_v();
     }
     if (owner) {
         if constexpr (BF) xh[tid] = f32_to_bf16(v);
@@ -609,7 +642,11 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     }
     __syncthreads();
     stamp(a.dbg, 3);
-    if constexpr (!BF) po.template issue<NT>(a.wo + (size_t)h * kD * kDh);
+    // the out-proj panel is requested BEHIND the q / k / v rows' dots: it has the whole attention phase to land, and at entry it
+    // would be 32 KB more (bf16) that every wave queues before it can park; on fp32 handles its 16 registers beside the 48 weight
+    // registers also spilled 11 (and a spilled load is a wait at the top of the kernel)
+    Panel<WT, kDh> po;
+    po.template issue<NT>(a.wo + (size_t)h * kD * kDh);
 
     // ---- single-pass attention over [0, n]: every thread owns the same rows of K and of V, so the
     //      scores never leave registers; each wave keeps a running (max, sum, P.V) and the 16 waves
@@ -627,7 +664,8 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     float m_run = -INFINITY, l_run = 0.f, acc[EPL];
 #pragma unroll
     for (int i = 0; i < EPL; ++i) acc[i] = 0.f;
-    const bool wave0 = __builtin_amdgcn_readfirstlane(wid) == 0;
+    const int awi = wid - AW0;             // this wave's attention index
+    const bool wave0 = __builtin_amdgcn_readfirstlane(wid) == AW0;
     if (AW == kNW || aw) {
     for (int c0 = 0; c0 == 0 || c0 < n; c0 += KCH * RPI) {
         if (c0 > 0) {
@@ -655,7 +693,7 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
             sv[it] = r < n ? s * scale : -INFINITY;
             cmax = max_nn(cmax, sv[it]);
         }
-        // the new token's own key/value (position n) rides with wave 0's first chunk; the other waves (fifteen of sixteen, all
+        // the new token's own key/value (position n) rides with the first chunk of attention wave 0 (wave AW0); the other attention waves (all
         // of them VALU-issue bound here) skip its score, exponential and eight FMAs, which contributed exact zeros
         const bool own = wave0 && c0 == 0;
         sv[KCH] = -INFINITY;
@@ -668,7 +706,7 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
                 for (int i = 0; i < EPL; ++i) s = fmaf(qr[i], qkv[32 + part * EPL + i], s);
             }
             s = group_sum<LPR>(s);
-            sv[KCH] = tid < LPR ? s * scale : -INFINITY;
+            sv[KCH] = tid - AW0 * 64 < LPR ? s * scale : -INFINITY;
             cmax = max_nn(cmax, sv[KCH]);
         }
         cmax = wave_max(cmax);
@@ -708,21 +746,21 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
         for (int i = 0; i < 2; ++i) r2[i] = halve16_sum(r4[i], r4[i + 2]);
         float r1 = halve8_sum(r2[0], r2[1]);
         r1 += lane_xor<4>(r1);
-        if ((lane & 4) == 0) pacc[wid * 32 + part * 8 + 4 * (lane >> 5) + 2 * ((lane >> 4) & 1) + ((lane >> 3) & 1)] = r1;
+        if ((lane & 4) == 0) pacc[awi * 32 + part * 8 + 4 * (lane >> 5) + 2 * ((lane >> 4) & 1) + ((lane >> 3) & 1)] = r1;
     } else {                       // fp32: 8 lanes per row; lane bits 5, 4 pick the dim, bit 3 is summed last
         float r2[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) r2[i] = halve32_sum(acc[i], acc[i + 2]);
         float r1 = halve16_sum(r2[0], r2[1]);
         r1 += lane_xor<8>(r1);
-        if ((lane & 8) == 0) pacc[wid * 32 + part * 4 + 2 * (lane >> 5) + ((lane >> 4) & 1)] = r1;
+        if ((lane & 8) == 0) pacc[awi * 32 + part * 4 + 2 * (lane >> 5) + ((lane >> 4) & 1)] = r1;
     }
-    if (lane == 0) { pm[wid] = m_run; pl[wid] = l_run; }
+    if (lane == 0) { pm[awi] = m_run; pl[awi] = l_run; }
     }   // aw
     stamp(a.dbg, 4);
     __syncthreads();
     if (wid == 0) {
-        // merge the AW waves: lane l (mod 16) owns wave l's (max, sum); 2x32 lanes own the 32 dims
+        // merge the AW waves, by attention index: lane l (mod 16) owns attention wave l's (max, sum); 2x32 lanes own the 32 dims
         const bool has = (lane & 15) < AW;
         const float mw = has ? pm[lane & 15] : -INFINITY, lw = has ? pl[lane & 15] : 0.f;
         const float M = row16_max(mw);
@@ -786,8 +824,6 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     raw16 w1r[RW][CPR];
 #pragma unroll
     for (int r = 0; r < RW; ++r) row_load<WT, NT>(a.w1 + (size_t)(row0 + r) * kD, w1r[r]);
-    Panel<WT, FJ> p2;
-    p2.template issue<NT>(a.w2p + (size_t)j * kD * FJ);
     const int oi = sumN_index<RW>();
     const float b1r = a.b1[row0 + oi];
     asm volatile("" : "+v"(ps.p[0][0]) : : "memory");
@@ -797,6 +833,11 @@ __global__ __launch_bounds__(kNT) void t2s_ffn_kernel(FfnArgs<WT> a) {
     stamp(a.dbg, 13);
     __syncthreads();
     stamp(a.dbg, 14);
+    // the W2 panel is not needed before the very end: requested behind the partial-sum barrier, it lands during the LayerNorm and
+    // the W1 dots instead of standing between a wave and its park()
+    Panel<WT, FJ> p2;
+    p2.template issue<NT>(a.w2p + (size_t)j * kD * FJ);
+    asm volatile("" : : : "memory");
     const float v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
     stamp(a.dbg, 15);
     if (owner) {
