@@ -385,7 +385,7 @@ FLAC_HD int flac_decode_frame(const unsigned char* p, uint32_t len, int channels
     return st;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(GSV_FLACDEC_NO_KERNEL)   // flacenc.h wants the scalar pieces only
 // one frame of the device table (built by gsv_flac_decode from the caller's host tables, 32 bytes)
 struct FlacFrameDev {
     long long byte_off;     // of the frame in the packed byte buffer

@@ -35,6 +35,7 @@ EXPORTS = [
     "gsv_roberta_forward", "gsv_roberta_features",
     "gsv_wav_to_mono", "gsv_wav_to_mono_batch",
     "gsv_flac_decode_workspace", "gsv_flac_decode", "gsv_flac_decode_host",
+    "gsv_flac_encode_bound", "gsv_flac_encode_workspace", "gsv_flac_encode", "gsv_flac_encode_host",
 ]
 
 
@@ -113,6 +114,27 @@ class FlacFrame(ctypes.Structure):
 
 
 FLAC_OPEN_END = 1       # GSV_FLAC_OPEN_END
+
+
+class FlacEncClip(ctypes.Structure):
+    """gsv_flac_enc_clip: one clip of gsv_flac_encode"""
+    _fields_ = [("in_offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("bits_per_sample", ctypes.c_int32)]
+
+
+class FlacEncFrame(ctypes.Structure):
+    """gsv_flac_enc_frame: one frame of gsv_flac_encode; header: the frame header through its CRC-8"""
+    _fields_ = [("clip", ctypes.c_int32), ("block_size", ctypes.c_int32), ("first_sample", ctypes.c_int32),
+                ("header_len", ctypes.c_int32), ("header", ctypes.c_uint8 * 16)]
+
+
+class FlacEncChoice(ctypes.Structure):
+    """gsv_flac_enc_choice: what a frame was coded with"""
+    _fields_ = [("kind", ctypes.c_uint8), ("order", ctypes.c_uint8), ("porder", ctypes.c_uint8), ("method", ctypes.c_uint8),
+                ("k", ctypes.c_uint8 * 64)]
+
+
+FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
+FLAC_ENC_MAX_BLOCK = 4608
 
 
 # GSV_FLAC_*: what a frame's status says
@@ -223,6 +245,8 @@ def lib():
         "gsv_wav_to_mono_batch": [vp, sz, ctypes.POINTER(WavClip), i, vp, vp],
         "gsv_flac_decode": [vp, sz, ctypes.POINTER(FlacClip), i, ctypes.POINTER(FlacFrame), i, vp, vp, vp, sz, vp],
         "gsv_flac_decode_host": [vp, sz, ctypes.POINTER(FlacClip), i, ctypes.POINTER(FlacFrame), i, vp, vp],
+        "gsv_flac_encode": [vp, sz, ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i, vp, sz, vp, vp, vp, sz, vp],
+        "gsv_flac_encode_host": [vp, sz, ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i, vp, sz, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -256,6 +280,9 @@ def lib():
     L.gsv_roberta_workspace.restype = sz
     L.gsv_flac_decode_workspace.argtypes = [ctypes.POINTER(FlacClip), i, i]
     L.gsv_flac_decode_workspace.restype = sz
+    for fn in (L.gsv_flac_encode_bound, L.gsv_flac_encode_workspace):
+        fn.argtypes = [ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i]
+        fn.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

@@ -9,10 +9,23 @@ path's own kernel.  A FLAC clip is bit-identical to the WAV file that holds the 
 Read: native FLAC, one or two channels, 8..24 bits per sample, fixed or variable block size.  More than two channels,
 32 bits per sample, Ogg-encapsulated FLAC and a file with an ID3v2 tag in front raise NotImplementedError.  The
 STREAMINFO MD5 is parsed and exposed (FlacInfo.md5) but NOT verified: that would need the integers back on the host.
-What is verified: each header's CRC-8 (here, while indexing) and each frame's CRC-16 (on the device).  No CPU path."""
+What is verified: each header's CRC-8 (here, while indexing) and each frame's CRC-16 (on the device).  No CPU path.
+
+Writing goes the other way: the container and every frame header are built here, the frames are encoded on
+the device (gsv_flac_encode, csrc/flacenc.h: one wave per frame) -- or by the same arithmetic on the CPU
+(gsv_flac_encode_host) when the device is a CPU or there is no GPU:
+
+    data = encode_flac(wave, 32000)                        # bytes of a .flac file: mono, 16 bits, blocks of 4096
+    files = encode_flacs([w0, w1], [32000, 44100], bits=[16, 24])   # one packed upload, one encode per 64 clips
+    save_flac("out.flac", wave, 32000)
+
+Written: native FLAC, fixed blocking, one channel, 16 or 24 bits, CONSTANT / FIXED / VERBATIM subframes chosen per frame
+by exact bit count.  load_flac(encode_flac(w)) is w bit for bit when w came from a file of that width.  The STREAMINFO
+MD5 is written as sixteen zero bytes ("not computed"): it would need the integers on the host."""
 import struct
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -271,3 +284,199 @@ def load_flacs(paths, device=None):
         res.append((out[s:s + info.n_samples], info.sample_rate))
         s += info.n_samples
     return res
+
+
+# ------------------------------------------------------------------------------------------------------------- writing
+_BLOCK_CODE = {v: k for k, v in list(_BLOCK.items()) + [(c, 256 << (c - 8)) for c in range(8, 16)]}
+_RATE_CODE = {v: k for k, v in _RATE.items()}
+_BITS_CODE = {v: k for k, v in _BITS.items()}
+ENC_MIN_BLOCK, ENC_MAX_BLOCK = 16, N.FLAC_ENC_MAX_BLOCK
+ENC_MAX_RATE = 655350
+
+
+def _coded_number(v) -> bytes:
+    """the UTF-8-style coding of a frame number of up to 31 bits, 1-6 bytes"""
+    if v < 0x80:
+        return bytes([v])
+    n = 2
+    while v >= 1 << (5 * n + 1):
+        n += 1
+    return bytes([(0xFF << (8 - n)) & 0xFF | (v >> (6 * (n - 1)))] + [0x80 | ((v >> (6 * i)) & 0x3F) for i in range(n - 2, -1, -1)])
+
+
+def build_header(block_size, rate, bits, number) -> bytes:
+    """the header of frame `number` of a mono fixed-blocking stream, CRC-8 included: the inverse of _header.  Block size
+    and rate take their table codes when they have one; otherwise the block size is explicit (8 or 16 bits) and the
+    rate code is 0 (from STREAMINFO)."""
+    if not 1 <= block_size <= 65536 or bits not in _BITS_CODE or not 0 <= number < 1 << 31:
+        raise ValueError("frame header of block size %d at %d bits, frame %d" % (block_size, bits, number))
+    bs_code = _BLOCK_CODE.get(block_size, 6 if block_size <= 256 else 7)
+    h = bytes([0xFF, 0xF8, bs_code << 4 | _RATE_CODE.get(rate, 0), _BITS_CODE[bits] << 1]) + _coded_number(number)
+    if bs_code == 6:
+        h += bytes([block_size - 1])
+    elif bs_code == 7:
+        h += struct.pack(">H", block_size - 1)
+    return h + bytes([_crc8(h)])
+
+
+def streaminfo(block_size, min_frame, max_frame, rate, bits, n_samples) -> bytes:
+    """the 34 bytes of a mono stream's STREAMINFO; the MD5 is sixteen zero bytes (not computed)"""
+    v = (rate << 44) | ((bits - 1) << 36) | n_samples
+    return (struct.pack(">HH", block_size, block_size) + min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big") +
+            v.to_bytes(8, "big") + bytes(16))
+
+
+_ENC_FRAME = np.dtype([("clip", "<i4"), ("block_size", "<i4"), ("first_sample", "<i4"), ("header_len", "<i4"), ("header", "u1", 16)])
+
+
+def enc_tables(lengths, rates, bits, block_sizes):
+    """the ctypes tables of one gsv_flac_encode / gsv_flac_encode_host call over clips packed back to back: every
+    clip's frames in order, each of its block size but the last -> (FlacEncClip array, FlacEncFrame array, [frames per
+    clip]).  The second array is a view of a numpy buffer that its `_buf` attribute keeps alive."""
+    clips = (N.FlacEncClip * len(lengths))()
+    rows, per_clip, at = [], [], 0
+    for c, (n, rate, b, bs) in enumerate(zip(lengths, rates, bits, block_sizes)):
+        clips[c] = N.FlacEncClip(at, n, b)
+        at += n
+        nf = (n + bs - 1) // bs
+        per_clip.append(nf)
+        for k in range(nf):
+            rows.append((c, min(bs, n - k * bs), k * bs, build_header(min(bs, n - k * bs), rate, b, k)))
+    tab = np.zeros(len(rows), dtype=_ENC_FRAME)
+    tab["clip"] = [r[0] for r in rows]
+    tab["block_size"] = [r[1] for r in rows]
+    tab["first_sample"] = [r[2] for r in rows]
+    tab["header_len"] = [len(r[3]) for r in rows]
+    tab["header"] = np.frombuffer(b"".join(r[3].ljust(16, b"\0") for r in rows), dtype=np.uint8).reshape(-1, 16)
+    ftab = (N.FlacEncFrame * len(rows)).from_buffer(tab)
+    ftab._buf = tab
+    return clips, ftab, per_clip
+
+
+def _per_clip(value, n, what):
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError("%d %s for %d clips" % (len(value), what, n))
+        return [int(v) for v in value]
+    return [int(value)] * n
+
+
+def _files(per_clip, lengths, rates, bits, block_sizes, offsets, data):
+    """frames packed back to back + their offsets -> one file's bytes per clip"""
+    out, f = [], 0
+    for nf, n, rate, b, bs in zip(per_clip, lengths, rates, bits, block_sizes):
+        sizes = [offsets[f + k + 1] - offsets[f + k] for k in range(nf)]
+        info = streaminfo(bs, min(sizes), max(sizes), rate, b, n)
+        out.append(b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info + bytes(data[offsets[f]:offsets[f + nf]]))
+        f += nf
+    return out
+
+
+def encode_flacs(waves, sample_rates, bits=16, block_size=4096, device=None):
+    """every clip of `waves` (1-D torch tensors or numpy arrays, fp32 in [-1, 1]) as the bytes of a FLAC file -> [bytes].
+    sample_rates, bits (16 | 24) and block_size (16..4608) are one value for all clips or one per clip.  The frames are
+    encoded on `device` (default: where the tensors are, else cuda:0 when there is a GPU, else the CPU): device tensors
+    that are views of one packed fp32 tensor are read in place, anything else is packed once (host arrays: one upload);
+    one gsv_flac_encode per AUX_MAX_CLIPS clips, its frame offsets and bytes read back once each.  On a CPU device
+    gsv_flac_encode_host does the same arithmetic, byte for byte.  ValueError, before any device work and naming the
+    clip's index, for an input that is not 1-D, an empty clip, bits other than 16 / 24, a block size or rate out of
+    range.  Each file is byte-identical to encode_flac of its clip."""
+    waves = list(waves)
+    n = len(waves)
+    rates, bits, bss = _per_clip(sample_rates, n, "sample rates"), _per_clip(bits, n, "bit widths"), _per_clip(block_size, n, "block sizes")
+    for c, (w, rate, b, bs) in enumerate(zip(waves, rates, bits, bss)):
+        if not isinstance(w, (torch.Tensor, np.ndarray)):
+            raise ValueError("clip %d: a %s (a 1-D torch tensor or numpy array is expected)" % (c, type(w).__name__))
+        if w.ndim != 1:
+            raise ValueError("clip %d: %d dimensions, shape %s (mono: one dimension)" % (c, w.ndim, tuple(w.shape)))
+        if w.shape[0] < 1 or w.shape[0] > 0x7FFFFFFF:
+            raise ValueError("clip %d: %d samples (1..2^31 - 1)" % (c, w.shape[0]))
+        if b not in (16, 24):
+            raise ValueError("clip %d: %d bits per sample (16 or 24 are written)" % (c, b))
+        if not ENC_MIN_BLOCK <= bs <= ENC_MAX_BLOCK:
+            raise ValueError("clip %d: block size %d (%d..%d)" % (c, bs, ENC_MIN_BLOCK, ENC_MAX_BLOCK))
+        if not 1 <= rate <= ENC_MAX_RATE:
+            raise ValueError("clip %d: sample rate %d Hz (1..%d)" % (c, rate, ENC_MAX_RATE))
+    if not waves:
+        return []
+    if device is not None:
+        dev = torch.device(device)
+    else:
+        on = [w.device for w in waves if isinstance(w, torch.Tensor) and w.device.type == "cuda"]
+        dev = on[0] if on else torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+    lengths = [int(w.shape[0]) for w in waves]
+    L = N.lib()
+    out = []
+    if dev.type != "cuda":
+        for c0 in range(0, n, N.AUX_MAX_CLIPS):
+            sl = slice(c0, c0 + N.AUX_MAX_CLIPS)
+            x = np.ascontiguousarray(np.concatenate([_host_f32(w) for w in waves[sl]]))
+            clips, ftab, per_clip = enc_tables(lengths[sl], rates[sl], bits[sl], bss[sl])
+            bound = L.gsv_flac_encode_bound(clips, len(clips), ftab, len(ftab))
+            data, offsets = np.empty(bound, dtype=np.uint8), np.empty(len(ftab) + 1, dtype=np.int64)
+            N.check(L.gsv_flac_encode_host(x.ctypes.data, len(x), clips, len(clips), ftab, len(ftab), data.ctypes.data, bound,
+                                           offsets.ctypes.data, None))
+            out += _files(per_clip, lengths[sl], rates[sl], bits[sl], bss[sl], offsets.tolist(), data)
+        return out
+    st = N.current_stream_ptr(dev)
+    for c0 in range(0, n, N.AUX_MAX_CLIPS):
+        sl = slice(c0, c0 + N.AUX_MAX_CLIPS)
+        clips, ftab, per_clip = enc_tables(lengths[sl], rates[sl], bits[sl], bss[sl])
+        x, base, total = _pack(waves[sl], dev)
+        if base is not None:                    # views of one tensor: where each clip starts in it
+            for c, w in enumerate(waves[sl]):
+                clips[c].in_offset = (w.data_ptr() - base) // 4
+        bound = L.gsv_flac_encode_bound(clips, len(clips), ftab, len(ftab))
+        need = L.gsv_flac_encode_workspace(clips, len(clips), ftab, len(ftab))
+        data = torch.empty(bound, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(len(ftab) + 1, dtype=torch.int64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        N.check(L.gsv_flac_encode(x.data_ptr() if base is None else base, total, clips, len(clips), ftab, len(ftab),
+                                  data.data_ptr(), bound, offsets.data_ptr(), None, ws.data_ptr(), need, st))
+        off = offsets.cpu().tolist()
+        out += _files(per_clip, lengths[sl], rates[sl], bits[sl], bss[sl], off, data[:off[-1]].cpu().numpy())
+    return out
+
+
+def _host_f32(w):
+    if isinstance(w, torch.Tensor):
+        w = w.detach().to("cpu", torch.float32).numpy()
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
+def _pack(waves, dev):
+    """the clips as one fp32 device buffer -> (tensor or None, base address or None, samples in it).  Tensors that are
+    already contiguous fp32 views of one storage on `dev` are read in place (base: the lowest address among them);
+    host arrays are concatenated on the host and go up in one copy; anything else is packed with one torch.cat."""
+    if all(isinstance(w, torch.Tensor) and w.device == dev and w.dtype == torch.float32 and w.is_contiguous() for w in waves):
+        if len({w.untyped_storage().data_ptr() for w in waves}) == 1:
+            base = min(w.data_ptr() for w in waves)
+            end = max(w.data_ptr() + 4 * w.shape[0] for w in waves)
+            return None, base, (end - base) // 4
+    if all(isinstance(w, np.ndarray) or w.device.type == "cpu" for w in waves):
+        x = torch.from_numpy(np.concatenate([_host_f32(w) for w in waves])).to(dev)
+    else:
+        x = torch.cat([(w.detach() if isinstance(w, torch.Tensor) else torch.from_numpy(_host_f32(w))).to(dev, torch.float32)
+                       for w in waves])
+    return x, None, x.shape[0]
+
+
+def encode_flac(wave, sample_rate, bits=16, block_size=4096, device=None) -> bytes:
+    """one clip as the bytes of a FLAC file (encode_flacs)"""
+    return encode_flacs([wave], [sample_rate], bits, block_size, device)[0]
+
+
+def save_flacs(paths, waves, sample_rates, bits=16, block_size=4096, device=None):
+    """encode_flacs, each clip written to its path"""
+    paths, waves = list(paths), list(waves)
+    if len(waves) != len(paths):
+        raise ValueError("%d paths for %d clips" % (len(paths), len(waves)))
+    files = encode_flacs(waves, sample_rates, bits, block_size, device)
+    for p, data in zip(paths, files):
+        with open(p, "wb") as f:
+            f.write(data)
+
+
+def save_flac(path, wave, sample_rate, bits=16, block_size=4096, device=None):
+    """one clip written as a FLAC file (encode_flacs)"""
+    save_flacs([path], [wave], [sample_rate], bits, block_size, device)

@@ -20,7 +20,9 @@ text loads it too).  Either sets tts_config.cnroberta, so a frontend written as
 logged and bert2 stays zeros.  Reference audio given as a path that names an existing WAV file (PCM or IEEE float, mono
 or stereo) or FLAC file (8..24 bits, mono or stereo) is read as TTS._load_audio reads it: the container parsed on the
 host, the samples converted to fp32 mono on the device (wavio.py) -- FLAC frames decoded there first (flacio.py) -- so
-infer("spk.wav", "prompt.flac", ...) works as in the reference.  What else sits in front of the
+infer("spk.wav", "prompt.flac", ...) works as in the reference.  Going out, AudioClip.save("x.flac") writes 16-bit FLAC
+whose frames are encoded on the device (flacio.py, csrc/flacenc.h; on the CPU by the same arithmetic without a GPU) and
+AudioClip.to_flac() returns those bytes; other extensions get the 16-bit WAV writer.  What else sits in front of the
 hot path in the reference -- G2P text frontends and decoding lossy compressed audio (mp3, ogg) -- is OUT OF SCOPE of this
 build (CPU string processing and third-party packages not installable here).  Their
 *outputs* enter through the same caches the reference keeps:
@@ -78,8 +80,10 @@ class Config:
 
 
 class AudioClip:
-    """Player.py:68-99 fields; playback needs `sounddevice`, saving uses `soundfile` when present
-    and falls back to a 16-bit PCM WAV writer."""
+    """Player.py:68-99 fields; playback needs `sounddevice`, saving uses `soundfile` when present.  Without it a path
+    ending in .flac is written as 16-bit FLAC, encoded on the GPU when there is one and by the same arithmetic on the CPU
+    otherwise (flacio.save_flac), and every other path by a 16-bit PCM WAV writer.  to_flac() returns the FLAC file's
+    bytes instead of writing them.  A saved .flac is valid reference audio: tts.infer("gen.flac", ...)."""
 
     def __init__(self, audio_queue, audio_data, samplerate, audio_len_s, subtitles, orig_text):
         self.audio_queue = audio_queue
@@ -100,15 +104,28 @@ class AudioClip:
             import soundfile as sf
             sf.write(save_path, self.audio_data, self.samplerate)
         except ImportError:
-            import wave
-            pcm = (np.clip(self.audio_data, -1.0, 1.0) * 32767.0).astype("<i2")
-            with wave.open(save_path, "wb") as w:
-                w.setnchannels(1); w.setsampwidth(2); w.setframerate(self.samplerate)
-                w.writeframes(pcm.tobytes())
+            if str(save_path).lower().endswith(".flac"):
+                from . import flacio
+                flacio.save_flac(save_path, self.audio_data, self.samplerate, bits=16)
+            else:
+                self._save_wav(save_path)
         if is_save_subtitles:
             import json
             with open(os.path.splitext(save_path)[0] + ".json", "w", encoding="utf-8") as f:
                 json.dump(self.subtitles, f, ensure_ascii=False, indent=2)
+
+    def to_flac(self, bits: int = 16) -> bytes:
+        """the clip as the bytes of a FLAC file (mono, `bits` 16 or 24, the quantiser of flacio.encode_flacs), for a
+        server that returns the file in a response: what save("x.flac") writes, without the file"""
+        from . import flacio
+        return flacio.encode_flac(self.audio_data, self.samplerate, bits=bits)
+
+    def _save_wav(self, save_path):
+        import wave
+        pcm = (np.clip(self.audio_data, -1.0, 1.0) * 32767.0).astype("<i2")
+        with wave.open(save_path, "wb") as w:
+            w.setnchannels(1); w.setsampwidth(2); w.setframerate(self.samplerate)
+            w.writeframes(pcm.tobytes())
 
 
 def cut_text(text: str, minlen: int = 10) -> list:

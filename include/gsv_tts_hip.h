@@ -599,6 +599,55 @@ int gsv_flac_decode(const void* bytes_dev, size_t n_bytes, const gsv_flac_clip* 
  * status: int32 [n_frames].  The same argument checks; out_offset is not used.  Needs no GPU. */
 int gsv_flac_decode_host(const void* bytes, size_t n_bytes, const gsv_flac_clip* clips, int n_clips,
                          const gsv_flac_frame* frames, int n_frames, int32_t* pcm_interleaved, int32_t* status);
+/* Writing FLAC: mono fp32 clips -> frames of native FLAC with fixed blocking at 16 or 24 bits per sample, encoded on the
+ * device (csrc/flacenc.h: one wave per frame).  The encoding has one right answer: the quantiser
+ * q = clamp(rint(x * 2^(bits-1))) with NaN -> 0; per frame CONSTANT when all samples are equal, else the FIXED order 0..4
+ * and Rice partition order 0..6 (each partition's best parameter, no escapes) with the fewest bits -- ties to the lower
+ * order, then the lower partition order -- or VERBATIM when that is strictly smaller.  The host builds the container and
+ * every frame's header, CRC-8 included (gsv_tts_lite_amd/flacio.py); the device copies the header in front of the
+ * subframe and closes the frame with its CRC-16.  The tables below are HOST arrays, read before the call returns. */
+typedef struct gsv_flac_enc_clip {
+    int64_t in_offset;         /* of the clip's first sample in `samples`, in samples */
+    int32_t n_samples;
+    int32_t bits_per_sample;   /* 16 or 24 */
+} gsv_flac_enc_clip;
+typedef struct gsv_flac_enc_frame {
+    int32_t clip;              /* index into the clip table */
+    int32_t block_size;        /* samples in this frame, 1..4608 */
+    int32_t first_sample;      /* within the clip */
+    int32_t header_len;        /* 6..16 bytes of `header`, through the CRC-8 */
+    uint8_t header[16];
+} gsv_flac_enc_frame;
+#define GSV_FLAC_ENC_CONSTANT 0
+#define GSV_FLAC_ENC_VERBATIM 1
+#define GSV_FLAC_ENC_FIXED 2
+/* what a frame was coded with: kind GSV_FLAC_ENC_*; for FIXED the predictor order, the partition order, the residual
+ * method (0 at 16 bits, 1 at 24) and k[j], partition j's Rice parameter for j < 2^porder; every other field 0 */
+typedef struct gsv_flac_enc_choice {
+    uint8_t kind, order, porder, method;
+    uint8_t k[64];
+} gsv_flac_enc_choice;
+/* the most bytes the frames of a table can take (every frame VERBATIM): what out_bytes must hold; 0 on bad arguments */
+size_t gsv_flac_encode_bound(const gsv_flac_enc_clip* clips, int n_clips, const gsv_flac_enc_frame* frames, int n_frames);
+/* device bytes of the workspace of gsv_flac_encode (the device frame table, one worst-case slot per frame, the
+ * lengths); 0 on bad arguments */
+size_t gsv_flac_encode_workspace(const gsv_flac_enc_clip* clips, int n_clips, const gsv_flac_enc_frame* frames, int n_frames);
+/* samples_dev: n_samples fp32 on the DEVICE; out_dev: the frames packed back to back, in table order; frame_offsets_dev:
+ * int64 [n_frames + 1] on the device, frame f at out_dev[frame_offsets[f], frame_offsets[f + 1]); choices_dev: [n_frames]
+ * on the device, or NULL.  Checked before anything is launched, each GSV_ERR_ARG with gsv_last_error naming the first bad
+ * entry: 1..GSV_AUX_MAX_CLIPS clips, each inside n_samples, bits 16 or 24, block sizes 1..4608, header_len 6..16, the
+ * frames of each clip (in table order) tiling [0, n_samples) exactly, out_bytes at least gsv_flac_encode_bound, the
+ * workspace large enough and 16-byte aligned.  One table upload and three launches (frames, scan, copy) on `stream`;
+ * no device memory is allocated (the device table is staged in a host vector).  The encoder has no data-dependent failure. */
+int gsv_flac_encode(const float* samples_dev, size_t n_samples, const gsv_flac_enc_clip* clips, int n_clips,
+                    const gsv_flac_enc_frame* frames, int n_frames, uint8_t* out_dev, size_t out_bytes,
+                    int64_t* frame_offsets_dev, gsv_flac_enc_choice* choices_dev, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* The same over HOST memory, frame after frame on the CPU from the same scalar pieces: the CPU path of flacio.encode_flacs
+ * and the device's oracle (device bytes equal host bytes).  The same argument checks; needs no GPU. */
+int gsv_flac_encode_host(const float* samples, size_t n_samples, const gsv_flac_enc_clip* clips, int n_clips,
+                         const gsv_flac_enc_frame* frames, int n_frames, uint8_t* out, size_t out_bytes,
+                         int64_t* frame_offsets, gsv_flac_enc_choice* choices);
 /* fbank frames of a waveform of n_samples at sample_rate once it is at 16 kHz: 1 + (n16 - 400) / 160, 0 if n16 < 400 */
 int gsv_sv_frames(gsv_sv* h, int n_samples, int sample_rate);
 /* device bytes of the caller-owned workspace of gsv_sv_embed over n_samples at sample_rate; it also covers
