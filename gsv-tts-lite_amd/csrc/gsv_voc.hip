@@ -198,6 +198,7 @@ int voc_flow_impl(gsv_voc* v, VocWs& w, const float* mask, int T, int Tg, hipStr
                     hipLaunchKernelGGL(flowmerge_tail_kernel, dim3(gt), dim3(256), 0, st, m);
                 }
                 HIPCHK(hipGetLastError());
+                voc_trace("flow_merged", C, T);
                 return GSV_OK;
             }
             const int ntiles = cdiv(T, FS_ROWS);
@@ -214,6 +215,7 @@ int voc_flow_impl(gsv_voc* v, VocWs& w, const float* mask, int T, int Tg, hipStr
                 hipLaunchKernelGGL((flowstage_kernel<FS_POST>), dim3(gx, 1), dim3(256), 0, st, a);
             }
             HIPCHK(hipGetLastError());
+            voc_trace("flow_staged", C, T);
             return GSV_OK;
         }
         HIPCHK(hipFuncSetAttribute((const void*)flowfuse_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FF_LDS_TOTAL));
@@ -243,6 +245,7 @@ int voc_flow_impl(gsv_voc* v, VocWs& w, const float* mask, int T, int Tg, hipStr
             }
         }
         HIPCHK(hipGetLastError());
+        voc_trace("flow_fused", C, T);
         return GSV_OK;
     }
     const int ew = std::min(2048, cdiv(T * H, 256));
@@ -271,6 +274,7 @@ int voc_flow_impl(gsv_voc* v, VocWs& w, const float* mask, int T, int Tg, hipStr
     }
     if (x != (AT*)w.zin) HIPCHK(hipMemcpyAsync(w.zin, x, sizeof(AT) * (size_t)T * C, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipGetLastError());
+    voc_trace("flow_unfused", C, T);
     return GSV_OK;
 }
 
@@ -306,8 +310,10 @@ int voc_dec_impl(gsv_voc* v, VocWs& w, int T, int Tg, float* out, hipStream_t st
         if (ru > 0) return ru;
         if (ru < 0) dma = false;   // no wups shape for this transposed conv (GSV_NO_WUPS, a stride / tap count outside its table): nobody writes the
                                    // activated copy, so the stage's resblock convs take the wconv / cgemm / tapgemm path below
-        if (ru < 0)
+        if (ru < 0) {
             if (int rc = run_conv<AT, AT, AT>(sg.up, x, ldi, Tc, xu, ldo, Tc, eu, st)) return rc;
+            voc_trace("tapgemm", sg.cout, Tn);
+        }
         if (sizeof(AT) == 2 && sg.rb_c && ldo == sg.rb_c) {
             // <= 32 channels: the three branches and their mean in ONE kernel, intermediates never leave the CU (rbfuse.h)
             RbFuseArgs ra;
@@ -322,6 +328,7 @@ int voc_dec_impl(gsv_voc* v, VocWs& w, int T, int Tg, float* out, hipStream_t st
                 HIPCHK(hipFuncSetAttribute((const void*)rbfuse_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RbShape<32>::LDS));
                 hipLaunchKernelGGL(rbfuse_kernel<32>, dim3(cdiv(Tn, RbShape<32>::BN)), dim3(512), RbShape<32>::LDS, st, ra);
             }
+            voc_trace("rbfuse", sg.rb_c, Tn);
             Tc = Tn;
             continue;
         }
@@ -368,8 +375,10 @@ int voc_dec_impl(gsv_voc* v, VocWs& w, int T, int Tg, float* out, hipStream_t st
             } else {
                 Epi e1; e1.in_slope = 0.1f;
                 if (int rc = run_conv_multi<AT, AT, AT>(b1, 3, ldo, Tn, ldo, Tn, e1, st)) return rc;
+                voc_trace("tapgemm", sg.cout, Tn);
                 Epi e2; e2.in_slope = 0.1f; e2.ld_res = ldo;
                 if (int rc = run_conv_multi<AT, AT, AT>(b2, 3, ldo, Tn, ldo, Tn, e2, st)) return rc;
+                voc_trace("tapgemm", sg.cout, Tn);
             }
             for (int j = 0; j < 3; ++j) cur[j] = (const AT*)b2[j].Y;
         }

@@ -10,6 +10,24 @@
 
 namespace {
 
+// GSV_VOC_TRACE=1: one stderr line per launch from the host launchers below and from gsv_voc.hip -- `[voc] <family> C=<channels> rows=<n>` --
+// so a test can assert WHICH kernel family ran a shape (tests/test_hip_vocoder_regimes.py).  Host side only, read once per process; off, it
+// is one predicted branch per launch: no synchronisation, no allocation, no launch.
+inline bool voc_trace_on() {
+    static const bool on = [] { const char* e = getenv("GSV_VOC_TRACE"); return e && *e && *e != '0'; }();
+    return on;
+}
+inline void voc_trace(const char* family, int C, int rows) {
+    if (voc_trace_on()) fprintf(stderr, "[voc] %s C=%d rows=%d\n", family, C, rows);
+}
+// Rows from which the 256-channel resblock convs run on cgemm.h instead of wdma.h (GSV_CGEMM256_MIN_ROWS=<n> moves the threshold: the tests
+// use it to put a few rows on the cgemm instantiation).  run_cgemm and wdma_shape both ask HERE, so the two can never disagree.
+constexpr int kCgemm256MinRows = 16384;
+inline int cgemm256_min_rows() {
+    static const int n = getenv("GSV_CGEMM256_MIN_ROWS") ? atoi(getenv("GSV_CGEMM256_MIN_ROWS")) : kCgemm256MinRows;
+    return n;
+}
+
 // The weights-in-registers path for the Generator's resblock convs (wconv.h).  Returns 1 when the
 // launch does not fit it (caller falls back to tapgemm): returns -1 then, 0 on success, > 0 = GSV_ERR_*.
 // wide resblock convs on the LDS-tiled GEMM (cgemm.h): 384 and 192 channels always, 256 channels from 16k rows on (below that
@@ -28,7 +46,7 @@ template <>
 inline int run_cgemm<bf16_t>(const Branch* brs, int ld, int n_rows, float in_slope, float out_slope, hipStream_t st, float* part, size_t part_bytes, int* flag) {
     static const bool off = getenv("GSV_NO_CGEMM") != nullptr;
     const int C = brs[0].pc->cout;
-    if (off || !(C == 384 || C == 192 || (C == 256 && n_rows >= 16384)) || ld != C) return -1;
+    if (off || !(C == 384 || C == 192 || (C == 256 && n_rows >= cgemm256_min_rows())) || ld != C) return -1;
     int order[3] = {0, 1, 2};
     for (int i = 0; i < 3; ++i) {
         const PackedConv& q = *brs[i].pc;
@@ -70,6 +88,7 @@ inline int run_cgemm<bf16_t>(const Branch* brs, int ld, int n_rows, float in_slo
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(tiles * (ns[0] + ns[1] + ns[2])), dim3(nt), lds, st, a);
         HIPCHK(hipGetLastError());
+        if (voc_trace_on()) fprintf(stderr, "[voc] cgemm C=%d rows=%d split=%d,%d,%d\n", C, n_rows, ns[0], ns[1], ns[2]);
         return GSV_OK;
     };
     if (C == 384) return launch(cgemm_kernel<384, 192, 128>, CgShape<384, 192, 128>::LDS, 128, CgShape<384, 192, 128>::TN, CgShape<384, 192, 128>::NT);
@@ -142,6 +161,7 @@ int run_wconv<bf16_t>(const Branch* brs, int ld, int n_rows, float in_slope, flo
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, a);
         HIPCHK(hipGetLastError());
+        voc_trace("wconv", C, n_rows);
         return GSV_OK;
     };
 #ifdef GSV_AB_KERNELS
@@ -167,7 +187,7 @@ inline bool wdma_shape(int C, int ld, int n_rows) {
 #else
     if (off && C != 256) return false;                            // 256 channels have no wconv.h kernel in the shipped library
 #endif
-    return C == 64 || C == 128 || (C == 256 && n_rows < 16384);
+    return C == 64 || C == 128 || (C == 256 && n_rows < cgemm256_min_rows());
 }
 inline int run_wdma(const Branch* brs, void* const* act, int ld, int n_rows, float out_slope, float act_slope, const void* zeros, void* sink, hipStream_t st) {
     const int C = brs[0].pc->cout;
@@ -207,6 +227,7 @@ inline int run_wdma(const Branch* brs, void* const* act, int ld, int n_rows, flo
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, a);
         HIPCHK(hipGetLastError());
+        voc_trace("wdma", C, n_rows);
         return GSV_OK;
     };
     if (C == 256) return launch(wdma_kernel<256, 2, 64, 2, 4>, wdma_lds_bytes<256, 2, 64, 2, 4>());
@@ -237,6 +258,7 @@ int run_wups<bf16_t>(const PackedConv& pc, const void* X, int ldx, int n_in, voi
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(a.nwalk * groups), dim3(256), lds, st, a);
         HIPCHK(hipGetLastError());
+        voc_trace("wups", pc.cout, n_in * pc.u);
         return GSV_OK;
     };
 #define GSV_WUPS(CIN, MS, BN, NT, PG, MAXB)                                                     \
