@@ -72,6 +72,15 @@ __device__ __forceinline__ void eos_publish(int32_t* eos_host, int slot, int val
 //    wave.  The deferred loads take issue slots while their wave would wait at a barrier anyway, and
 //    still land ahead of their use (profiles/decode_load_staging.txt: last wave past the pin at 3.9k
 //    cycles instead of 6.0k, the attention block 13.7k -> 12.6k, the FFN block 5.5k -> 5.3k);
+//  * the same holds for the first GEMV's weight rows of the waves that own no LayerNorm element (bf16 attention kernel, MODE 1, 64 slices): with
+//    all 96 QKV row loads at entry the last wave parked 1.4k cycles behind wave 0, and the LayerNorm consumes none of them.  The
+//    eight attention waves request their rows behind the partial-sum barrier, then their K rows, and their V rows behind their QKV
+//    dots; each wave role runs its own copy of the code up to the dots so that each has its own counted waits (ROLES in
+//    t2s_attn_kernel).  What bounds that barrier afterwards is the arrival of the partial rows themselves (written on other XCDs):
+//    the last wave has them 3.4k cycles in with nothing but partial rows in front of it.  How much the attention waves may queue
+//    behind the barrier is bounded too: the next barrier waits for THEIR issue, about 16 cycles per load on 8 waves, against the
+//    owners' finish() + LayerNorm, 1.26k cycles (profiles/decode_park_order.txt: attention block 13.0k -> 12.0k cycles; the FFN
+//    kernel's W1 rows, two per wave, measured no different in either place and stay at entry);
 //  * hipcc counts a wait by the path with the FEWEST loads behind the awaited one (vmcnt is one in-order
 //    counter): where only some waves issue a load group (K/V), every wait behind it also covers that
 //    group on those waves.  So such a group goes where nothing issued earlier is awaited for long;
@@ -80,9 +89,10 @@ __device__ __forceinline__ void eos_publish(int32_t* eos_host, int slot, int val
 //    4 waves per SIMD share the rows/keys, each wave's stream is a quarter of a 256-thread block's.
 
 // optional phase timestamps (bring-up aid): in block (0,0) the first lane of wave 0 writes clock64() into dbg[slot], the
-// first lane of the last wave into dbg[16 + slot] (32 slots)
+// first lane of the last wave into dbg[16 + slot]; slots from 16 on go to dbg[32 + 2 (slot - 16)] and the entry behind it (64 entries)
 __device__ __forceinline__ void stamp(unsigned long long* dbg, int slot) {
-    if (dbg != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x == 0 || threadIdx.x == 960)) dbg[slot + (threadIdx.x ? 16 : 0)] = clock64();
+    if (dbg != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x == 0 || threadIdx.x == 960))
+        dbg[slot < 16 ? slot + (threadIdx.x ? 16 : 0) : 32 + 2 * (slot - 16) + (threadIdx.x ? 1 : 0)] = clock64();
 }
 
 constexpr int kNT = 1024;       // threads per decode block
@@ -538,33 +548,57 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
     // without this rendezvous the last wave's partial rows queue behind the first waves' weights
     if constexpr (MODE == 1) __builtin_amdgcn_s_barrier();
     asm volatile("" : : : "memory");
+    // ROLES (bf16 handles, MODE 1): the eight waves that own a LayerNorm element and the eight attention waves each run their own
+    // copy of the code from here to the QKV dots.  A wave reaches park() only once it has issued every load in front of it, and
+    // the partial-sum barrier waits for the last wave, so the attention waves request their QKV rows BEHIND that barrier, in front
+    // of their K rows -- they own no LayerNorm element and would only wait there -- and only the owner waves' 48 row loads stand
+    // between the partial rows and a park().  One copy per role, because hipcc counts a vmcnt wait by the path with the fewest
+    // younger loads, and a join merges the paths: in code common to both roles the waits in front of park() would also cover the
+    // owner waves' weight rows, and the waits in front of the dots the attention waves' K/V rows.  (In the ISA: owner waves
+    // vmcnt(10..7) in front of park() and (6..0) in front of the dots; attention waves drain their partial rows, nothing else, in
+    // front of park() and wait vmcnt(10..4) in front of the dots, the V rows issued behind them.)
+    // At up to four sequences only (64 slices, four partial rows per wave in front of the weight rows).  With 32 slices the step
+    // measured no faster at 16 sequences and 1 % slower at 8 (0.269 -> 0.272 ms), so those instantiations keep one copy and every
+    // weight row at entry.
+    constexpr bool ROLES = MODE == 1 && AW0 > 0 && NJ == kNJFine;
     const WT* wp = a.wqkv + ((size_t)h * 96 + wid * RW) * kD;
     raw16 wq[RW][CPR];
-#pragma unroll
-    for (int r = 0; r < RW; ++r) row_load<WT, NT>(wp + (size_t)r * kD, wq[r]);
+    float bq;
     const int oi = sumN_index<8>();
-    const float bq = a.bqkv[h * 96 + wid * RW + min(oi, RW - 1)];
+    auto issue_wq = [&]() {
+#pragma unroll
+        for (int r = 0; r < RW; ++r) row_load<WT, NT>(wp + (size_t)r * kD, wq[r]);
+        bq = a.bqkv[h * 96 + wid * RW + min(oi, RW - 1)];
+    };
+    int n, nw;
     // Pin "the entry loads issued, THEN arithmetic": the opaque asm redefines the head of the partial-sum
     // chain, so no add can be scheduled above it, while the memory clobber keeps every load above
     // it.  It only needs the FIRST-issued loads to have landed (kv_len among them: its first use sits here).
-    stamp(a.dbg, 7);
-    if constexpr (MODE == 0) asm volatile("" : "+v"(xd), "+v"(kvl_raw) : : "memory");
-    else if constexpr (MODE == 2) asm volatile("" : "+v"(tl.tp.v), "+v"(kvl_raw) : : "memory");
-    else asm volatile("" : "+v"(ps.p[0][0]), "+v"(kvl_raw) : : "memory");
-    stamp(a.dbg, 1);
-    int n = kvl_raw;
-    // kv_len < 0 = a PARKED slot (include/gsv_tts_hip.h, staged refill): its K/V row goes to the last row of the cache,
-    // which no prompt pass writes, and it attends over row 0 only -- it must not touch rows a concurrent refill fills
-    const int nw = n < 0 ? a.T - 1 : (n > a.T - 1 ? a.T - 1 : n);
-    if (n > a.T - 1) n = a.T - 1;  // memory safety only; the host never steps a full cache
-    if (n < 0) n = 0;
-    // The first chunk's K/V rows, DEFERRED: the attention waves request them once the partial rows are parked (MODE 1) or the layer
+    auto pin = [&]() {
+        stamp(a.dbg, 7);
+        if constexpr (MODE == 0) asm volatile("" : "+v"(xd), "+v"(kvl_raw) : : "memory");
+        else if constexpr (MODE == 2) asm volatile("" : "+v"(tl.tp.v), "+v"(kvl_raw) : : "memory");
+        else asm volatile("" : "+v"(ps.p[0][0]), "+v"(kvl_raw) : : "memory");
+        stamp(a.dbg, 1);
+        n = kvl_raw;
+        // kv_len < 0 = a PARKED slot (include/gsv_tts_hip.h, staged refill): its K/V row goes to the last row of the cache,
+        // which no prompt pass writes, and it attends over row 0 only -- it must not touch rows a concurrent refill fills
+        nw = n < 0 ? a.T - 1 : (n > a.T - 1 ? a.T - 1 : n);
+        if (n > a.T - 1) n = a.T - 1;  // memory safety only; the host never steps a full cache
+        if (n < 0) n = 0;
+    };
+    if constexpr (!ROLES) {
+        issue_wq();
+        pin();
+    }
+    // The first chunk's K/V rows, DEFERRED: the attention waves request them once the partial rows are parked (MODE 1; with ROLES the V rows
+    // behind the QKV dots) or the layer
     // input is on its way to LDS, not at entry, where every wave of the block would have to queue them before it could park.
     // They are loaded UNCONDITIONALLY from a clamped (always valid) row and masked at use: a per-element "load or zero" select
     // makes hipcc branch around each load and drain vmcnt(0).  A deferred load may run after this block's own append to row
     // nw; a register loaded from a row >= n is never used unmasked, so what it then holds does not matter.
     raw16 kreg[KCH], vreg[KCH];
-    // (issue_k has no compiler barrier of its own: every call is followed by issue_v's or by ln512's barrier -- keep it so)
+    // (issue_k has no compiler barrier of its own: every call is followed by issue_v's or by a block barrier -- keep it so)
     auto issue_k = [&]() {
         if (AW == kNW || aw) {
 #pragma unroll
@@ -579,38 +613,9 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
         asm volatile("" : : : "memory");
     };
 
-    // ---- layer input
-    float v;
-    if constexpr (MODE == 0) {
-        v = xd;
-    } else if constexpr (MODE == 2) {
-        v = steptok_finish(a.tk, tl, b, lane, tid, owner, (int64_t)kvl_raw, a.T, h == 0 && tid == 0);   // (a second load of kv_len here drained the load counter)
-    } else {
-        ps.park(stage);
-        __syncthreads();
-        // attention waves that own no LayerNorm element (bf16) request K and V here and then only meet the barriers; where every wave
-        // is both (fp32), V waits behind the LayerNorm's barrier so that the owners' statistics do not queue behind it
-        issue_k();
-        if constexpr (AW0 > 0) issue_v();
-        v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
-        if constexpr (AW0 == 0) issue_v();
-    }
-    if constexpr (MODE != 1) {
-        asm volatile("" : "+v"(v) : : "memory");
-        issue_k();
-        issue_v();
-    }
-    if (owner) {
-        if constexpr (BF) xh[tid] = f32_to_bf16(v);
-        else xs[tid] = v;
-        if (h == 0) a.xout[(size_t)b * kD + tid] = v;
-    }
-    __syncthreads();
-    stamp(a.dbg, 2);
-
     // ---- q, k, v of this head: 96 rows, 6 per wave.  k and v are rounded through the cache type
     //      (this step must see exactly what later steps read back) and appended at position n.
-    {
+    auto qkv_rows = [&]() {
         float acc[8];
         if constexpr (BF) {
             const raw16 x = x8_load(xh, lane * 8);
@@ -639,6 +644,69 @@ __global__ __launch_bounds__(kNT) void t2s_attn_kernel(AttnArgs<WT> a) {
                 qkv[row] = val;
             }
         }
+    };
+
+    // ---- layer input
+    float v;
+    if constexpr (ROLES) {
+        // the same steps as below, once per role; either side meets the same four barriers
+        if (aw) {
+            pin();
+            ps.park(stage);
+            stamp(a.dbg, 16);
+            __syncthreads();             // the partial-sum barrier
+            // 48 weight-row and 32 K-row loads (1.3k cycles of issue) fit the owner waves' finish() + LayerNorm; the V rows on top of
+            // them, or everything one barrier later, kept the owners waiting at the next barrier (profiles/decode_park_order.txt)
+            issue_wq();
+            issue_k();
+            __syncthreads();             // the LayerNorm's barrier: these waves own no element of it
+            __syncthreads();             // xs written
+            stamp(a.dbg, 2);
+            qkv_rows();
+            issue_v();                   // first used a thousand cycles into the attention phase; behind the next barrier they came too late
+            asm volatile("; attention waves" : : : "memory");   // (the two copies must stay two: see ROLES)
+        } else {
+            issue_wq();
+            pin();
+            ps.park(stage);
+            stamp(a.dbg, 16);
+            __syncthreads();
+            v = ln512<BF>(ps.finish(stage), true, ps.lng, ps.lnb, red);
+            xh[tid] = f32_to_bf16(v);
+            if (h == 0) a.xout[(size_t)b * kD + tid] = v;
+            __syncthreads();
+            stamp(a.dbg, 2);
+            qkv_rows();
+            asm volatile("; owner waves" : : : "memory");
+        }
+    } else {
+        if constexpr (MODE == 0) {
+            v = xd;
+        } else if constexpr (MODE == 2) {
+            v = steptok_finish(a.tk, tl, b, lane, tid, owner, (int64_t)kvl_raw, a.T, h == 0 && tid == 0);   // (a second load of kv_len here drained the load counter)
+        } else {
+            ps.park(stage);
+            __syncthreads();
+            // attention waves that own no LayerNorm element (bf16) request K and V here and then only meet the barriers; where every wave
+            // is both (fp32), V waits behind the LayerNorm's barrier so that the owners' statistics do not queue behind it
+            issue_k();
+            if constexpr (AW0 > 0) issue_v();
+            v = ln512<BF>(owner ? ps.finish(stage) : 0.f, owner, ps.lng, ps.lnb, red);
+            if constexpr (AW0 == 0) issue_v();
+        }
+        if constexpr (MODE != 1) {
+            asm volatile("" : "+v"(v) : : "memory");
+            issue_k();
+            issue_v();
+        }
+        if (owner) {
+            if constexpr (BF) xh[tid] = f32_to_bf16(v);
+            else xs[tid] = v;
+            if (h == 0) a.xout[(size_t)b * kD + tid] = v;
+        }
+        __syncthreads();
+        stamp(a.dbg, 2);
+        qkv_rows();
     }
     __syncthreads();
     stamp(a.dbg, 3);

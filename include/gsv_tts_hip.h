@@ -262,8 +262,9 @@ size_t gsv_t2s_device_bytes(gsv_t2s* h);
  * token's pre_tokens / seen / eos_at entries and the partial-sum scratch, all of which the next real step
  * (or prefill) overwrites -- call it between utterances, not inside one. */
 int gsv_t2s_time_kernels(gsv_t2s* h, int batch, int iters, float* out_ms, void* stream);
-/* Bring-up aid: when `buf` (device, >= 32 x uint64) is non-null the LAST layer's attn/ffn kernels
- * write shader-clock timestamps of their phases into it (slots 0-6 attn, 8-15 ffn: the block's first wave; + 16: its last). */
+/* Bring-up aid: when `buf` (device, >= 64 x uint64) is non-null the LAST layer's attn/ffn kernels
+ * write shader-clock timestamps of their phases into it (slots 0-7 attn, 8-15 ffn: the block's first wave; + 16: its last;
+ * attn slot 16, behind park(): entries 32 / 33). */
 int gsv_t2s_set_debug(gsv_t2s* h, void* buf);
 /* materialise the pending token of every slot into pre_tokens/seen/eos_at (idempotent) */
 int gsv_t2s_flush(gsv_t2s* h, int batch, void* stream);

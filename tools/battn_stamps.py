@@ -10,7 +10,7 @@ dev = torch.device("cuda:0")
 cfg = synth.gpt_config(); m = Text2SemanticDecoder(cfg); m.load_state_dict(synth.gpt_weights(cfg, seed=1, eos_gain=-8.0))
 m.initialize_runtime(torch.bfloat16, dev, [(B, T)])
 rs = [synth.synth_request(i, 40, 60, 100, seed=1) for i in range(B)]
-dbg = torch.zeros(32, dtype=torch.int64, device=dev)
+dbg = torch.zeros(64, dtype=torch.int64, device=dev)
 N.check(N.lib().gsv_t2s_set_debug(m._h, dbg.data_ptr()))
 with torch.inference_mode():
     xy, xl, yl, _, _ = m.embed_prompt([torch.from_numpy(r[0]).to(dev) for r in rs], [torch.from_numpy(r[1]).to(dev) for r in rs], [torch.from_numpy(r[2]).to(dev) for r in rs])
