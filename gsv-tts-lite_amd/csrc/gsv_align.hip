@@ -102,4 +102,30 @@ int gsv_sola(const float* prev_tail, const float* chunk, int n, int overlap, int
     return GSV_OK;
 }
 
+// ---- chunk epilogue of a stream (sola.h): score, decide, copy
+size_t gsv_stream_emit_workspace(int search_len, int n) { return n < 0 ? 0 : gsv_sola_workspace(search_len); }
+
+int gsv_stream_emit(const float* prev_tail, const float* chunk, int n, int overlap, int search_len, int is_final, int trim_head,
+                    int mute_samples, float* out, float* tail_out, int32_t* rec, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!chunk || !out || !tail_out || !rec || !workspace) return abi_fail(GSV_ERR_ARG, "stream_emit: null argument");
+    if (n < 0 || overlap < (prev_tail ? 1 : 0) || search_len < 0 || mute_samples < 0 || n < overlap ||
+        (long long)n + mute_samples + overlap > 0x7fffffffLL)
+        return abi_fail(GSV_ERR_ARG, "stream_emit: chunk of %d samples, overlap %d, search %d, mute %d", n, overlap, search_len, mute_samples);
+    if (prev_tail == tail_out) return abi_fail(GSV_ERR_ARG, "stream_emit: tail_out aliases prev_tail");
+    const int n_off = (n < overlap + search_len ? n : overlap + search_len) - overlap + 1;
+    if (workspace_bytes < (size_t)n_off * sizeof(float))
+        return abi_fail(GSV_ERR_ARG, "stream_emit workspace %zu < %zu", workspace_bytes, (size_t)n_off * sizeof(float));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* score = static_cast<float*>(workspace);
+    if (prev_tail) hipLaunchKernelGGL(sola_score_kernel, dim3(n_off), dim3(256), 0, st, prev_tail, chunk, overlap, score);
+    hipLaunchKernelGGL(stream_emit_decide_kernel, dim3(1), dim3(kEmitWaves * 64), 0, st, prev_tail, chunk, n, overlap, (const float*)score,
+                       n_off, is_final, trim_head, mute_samples, rec);
+    const long long total = (long long)n + mute_samples + overlap;      // the most the copy writes
+    const long long blocks = (total + 256 * 8 - 1) / (256 * 8);
+    hipLaunchKernelGGL(stream_emit_copy_kernel, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks))), dim3(256), 0, st, prev_tail,
+                       chunk, n, overlap, is_final, (const int*)rec, out, tail_out);
+    if (hipGetLastError() != hipSuccess) return abi_fail(GSV_ERR_HIP, "stream_emit: launch failed");
+    return GSV_OK;
+}
+
 }  // extern "C"

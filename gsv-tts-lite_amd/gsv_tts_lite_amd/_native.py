@@ -23,7 +23,7 @@ EXPORTS = [
     "gsv_voc_create", "gsv_voc_destroy", "gsv_voc_load_tensor", "gsv_voc_finalize", "gsv_voc_workspace",
     "gsv_voc_flow_dec", "gsv_voc_flow_dec_graph", "gsv_voc_resample_linear", "gsv_voc_flow", "gsv_voc_dec", "gsv_voc_has_enc_p", "gsv_voc_enc_workspace", "gsv_voc_enc_p", "gsv_voc_decode_workspace", "gsv_voc_decode",
     "gsv_voc_decode_segments_workspace", "gsv_voc_decode_segments",
-    "gsv_align_workspace", "gsv_align_viterbi", "gsv_sola_workspace", "gsv_sola",
+    "gsv_align_workspace", "gsv_align_viterbi", "gsv_sola_workspace", "gsv_sola", "gsv_stream_emit_workspace", "gsv_stream_emit",
     "gsv_ref_create", "gsv_ref_destroy", "gsv_ref_load_tensor", "gsv_ref_finalize", "gsv_ref_workspace",
     "gsv_ref_spectrogram", "gsv_ref_get_ge", "gsv_ref_extract_latent",
     "gsv_hubert_create", "gsv_hubert_destroy", "gsv_hubert_load_tensor", "gsv_hubert_finalize", "gsv_hubert_frames",
@@ -209,6 +209,7 @@ def lib():
         "gsv_voc_decode_segments": [vp, vp, i, vp, i, vp, i, vp, ctypes.POINTER(VocSegment), i, vp, vp, vp, sz, vp],
         "gsv_align_viterbi": [vp, i, i, i, vp, vp, sz, vp],
         "gsv_sola": [vp, vp, i, i, i, vp, vp, vp, sz, vp],
+        "gsv_stream_emit": [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, sz, vp],
         "gsv_ref_create": [ctypes.POINTER(RefConfig), ctypes.POINTER(vp)],
         "gsv_ref_destroy": [vp],
         "gsv_ref_load_tensor": [vp, ctypes.c_char_p, vp, i64, vp],
@@ -287,6 +288,8 @@ def lib():
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]
     L.gsv_sola_workspace.restype = sz
+    L.gsv_stream_emit_workspace.argtypes = [i, i]
+    L.gsv_stream_emit_workspace.restype = sz
     _LIB = L
     return L
 

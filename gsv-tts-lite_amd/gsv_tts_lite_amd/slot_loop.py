@@ -58,7 +58,15 @@ class SlotLoop:
     left it, tokens(slot, first row, count) -> a copy, park(slot).  A policy (subclass) supplies `ended(slot)`: what becomes of
     a slot that ended; `before_window(block)`: slots take requests (block: no slot is live, nothing to overlap a wait with);
     `after_window()`: host work behind the steps the GPU is busy with; `idle()`: no slot is live and every read-back has been
-    examined -- True if slots may still take requests."""
+    examined -- True if slots may still take requests.
+
+    Streaming (`stream_chunk` set by the driver, Text2SemanticDecoder.infer_stream_batched): when a window's read-back is examined,
+    `on_chunks` receives [(request, cumulative token rows -- a copy --, is_final)] for the slots whose count of certainly valid
+    tokens has passed a multiple of `stream_chunk` (no EOS among samples 0 .. steps: `steps` tokens are valid), in order, and for
+    the requests that ended.  The rows are copied while the slot still holds them: from the live slot, or from what was saved when
+    the host ended it.  An end is seen one window late, so a chunk lags by up to `check_interval` steps; it never holds a token at
+    or behind the EOS.  After an EOS at sample e the final rows are samples 0 .. e - 1 (`infer_stream`'s final chunk, which
+    starts with the sample `collect` drops); after a host end they are what `collect` gets."""
 
     def __init__(self, stepped, B, first, first_len, cap, check_interval, budgets, nxt, exhausted, prompt_len, on_finish):
         self.stepped, self.B, self.cap, self.check_interval, self.budgets = stepped, B, cap, check_interval, budgets
@@ -70,9 +78,11 @@ class SlotLoop:
         self.steps = [0] * B                            # steps issued since the slot joined
         self.joined = [0] * B                           # first window whose read-back shows the slot's current request
         self.window, self.idx = 0, 0
-        self.to_cut = []        # (window, slot, request, saved tokens, most tokens): ended by the host, tokens not cut yet
+        self.to_cut = []        # (window, slot, request, saved tokens, most tokens, the saved rows: with sample 0 in front when streaming): ended by the host, tokens not cut yet
         self.snaps = []         # (window, buffer, event): read-backs not examined yet, two buffers in turn
         self.pred, self.orig = [], []
+        self.stream_chunk, self.on_chunks = None, None
+        self.handed = {}        # request -> chunk boundaries handed to on_chunks so far
         self.last_stats = {"slots": B, "steps": 0, "kv_rows": 0, "prefill_rows": len(first), "refills": 0,
                            "slot_steps": 0, "live_slot_steps": 0}
 
@@ -112,22 +122,52 @@ class SlotLoop:
             if n_max is not None:
                 # the slot may decode another request from the next window on: its tokens are saved now (behind this
                 # window's steps on the stream), cut at the first EOS when the window's read-back is in
-                saved = self.stepped.tokens(i, self.start[i] + 1, n_max)
-                self.to_cut.append((self.window, i, self.req[i], saved, n_max))
+                lead = 1 if self.stream_chunk else 0        # a stream's final chunk behind an EOS starts with sample 0
+                rows = self.stepped.tokens(i, self.start[i] + 1 - lead, n_max + lead)
+                self.to_cut.append((self.window, i, self.req[i], rows[lead:], n_max, rows))
                 self.ended(i)
-        self.snaps.append((self.window, buf, ev))
+        self.snaps.append((self.window, buf, ev, list(self.steps) if self.stream_chunk else None))
 
-    def examine(self, window, buf, ev):
-        """read-back of `window` (taken after its steps): cut what the host ended at that boundary, find EOS ends"""
+    def boundaries(self, out, r, valid, rows):
+        """the chunk boundaries of request `r` that `valid` tokens pass; rows(n) -> a copy of its first n tokens"""
+        k = self.handed.get(r, 0)
+        while (k + 1) * self.stream_chunk <= valid:
+            k += 1
+            out.append((r, rows(k * self.stream_chunk), False))
+        self.handed[r] = k
+
+    def examine(self, window, buf, ev, steps=None):
+        """read-back of `window` (taken after its steps; `steps`: per slot, issued up to it): cut what the host ended at that
+        boundary, find EOS ends, hand out the chunks of a stream"""
         eos = self.stepped.eos(buf, ev)
+        out = []
         for rec in [c for c in self.to_cut if c[0] == window]:
-            _, i, r, saved, n_max = rec
-            self.collect(r, saved[: max(0, kept(n_max, eos[i]))].clone())
+            _, i, r, saved, n_max, rows = rec
+            keep = max(0, kept(n_max, eos[i]))
+            self.collect(r, saved[:keep].clone())
             self.to_cut.remove(rec)
+            if self.stream_chunk:
+                self.boundaries(out, r, keep, lambda n: saved[:n].clone())
+                self.handed.pop(r)
+                out.append((r, rows[: eos[i]].clone() if 1 <= eos[i] <= n_max + 1 else saved[:keep].clone(), True))
         for i in range(self.B):
-            if self.state[i] == LIVE and self.joined[i] <= window and eos[i] >= 0:
-                self.collect(self.req[i], self.stepped.tokens(i, self.start[i] + 1, eos[i] - 1))
+            if self.state[i] != LIVE or self.joined[i] > window:
+                continue
+            r, e = self.req[i], eos[i]
+            if e >= 0 and not self.stream_chunk:
+                self.collect(r, self.stepped.tokens(i, self.start[i] + 1, e - 1))
                 self.ended(i)
+            elif e >= 0:
+                rows = self.stepped.tokens(i, self.start[i], e)         # samples 0 .. e - 1
+                self.collect(r, rows[1:])
+                self.boundaries(out, r, max(0, e - 1), lambda n: rows[1: 1 + n].clone())
+                self.handed.pop(r)
+                out.append((r, rows, True))
+                self.ended(i)
+            elif self.stream_chunk:
+                self.boundaries(out, r, steps[i], lambda n: self.stepped.tokens(i, self.start[i] + 1, n))
+        if out:
+            self.on_chunks(out)
 
     def drain(self):
         while self.snaps:
@@ -135,10 +175,17 @@ class SlotLoop:
 
     def run(self):
         """-> (tokens per request in completion order, their request indices); ends when `idle` says nothing is left"""
+        for _ in self.windows():
+            pass
+        return self.pred, self.orig
+
+    def windows(self):
+        """`run` as a generator: yields wherever read-backs have been examined (a stream's chunks are with `on_chunks` by then)"""
         while True:
             live = LIVE in self.state
             if not live:
                 self.drain()                        # nothing is running that the read-backs could hide behind
+                yield
             self.before_window(block=not live)
             if LIVE not in self.state:
                 if self.idle():
@@ -149,9 +196,38 @@ class SlotLoop:
             while len(self.snaps) > 1:              # the PREVIOUS window's read-back: on the host by now
                 self.examine(*self.snaps.pop(0))
             self.window += 1
+            yield
         self.drain()
         assert not self.to_cut
-        return self.pred, self.orig
+
+
+def stream_chunks(loop, stream_chunk, boost, ticks=False):
+    """`infer_stream`'s chunk protocol (t2s_model.py:466-553) over the windows of a slot loop: a generator of (request, cumulative
+    token rows, is_final).  The loop reports when a request's valid tokens pass a multiple of `stream_chunk` (`on_chunks`); a
+    request's chunk is sent when its NEXT one is known -- the first at once if boost[request] -- and the final rows end it.  The
+    windows are issued inside torch.inference_mode; the consumer runs outside it, between two windows.  `ticks`: (None, None,
+    False) behind every window as well, for a consumer with work of its own to poll while the slots decode."""
+    chunks, state = [], {}          # state: request -> (no chunk sent yet, the chunk held back)
+    loop.stream_chunk, loop.on_chunks = stream_chunk, chunks.extend
+    windows, running = loop.windows(), True
+    while running:
+        with torch.inference_mode():
+            running = next(windows, False) is None
+        for r, rows, is_final in chunks[:]:
+            first, held = state.pop(r, (True, None))
+            if is_final:
+                yield r, rows, True
+                continue
+            if held is not None:
+                yield r, held, False
+            held = rows
+            if boost[r] and first:
+                first, held = False, None
+                yield r, rows, False
+            state[r] = (first, held)
+        del chunks[:]
+        if ticks and running:
+            yield None, None, False
 
 
 class _Stepped:

@@ -4,7 +4,11 @@ The reference (gsv_tts/TTS.py:429-436) aligns each new chunk to the previous chu
 normalised cross-correlation over 320 candidate offsets + a linear cross-fade, three torch ops and an `.item()`), keeps the last
 `overlap` samples back, and hands out the rest.  Here that is one library call per chunk (`gsv_sola`, csrc/sola.h: a score launch
 with one block per offset and a splice launch) driven by `ChunkSplicer`, which owns the tail between chunks.  There is no torch
-compute on this path and no CPU fallback."""
+compute on this path and no CPU fallback.
+
+`ChunkEmitter` is the same splice for a loop that serves many streams (TTS.infer_stream_batched) and may not wait for the device:
+`gsv_stream_emit` also trims the head of a segment's first chunk and appends the mute behind its last, decides the chunk's length on
+the device, and the samples reach the host by one asynchronous copy behind a handle."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -47,3 +51,70 @@ class ChunkSplicer:
             self.offsets.append(k)
         self.tail = x[-self.overlap:].clone()
         return x if is_final else x[:-self.overlap]
+
+
+class _Emitted:
+    """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
+
+    def __init__(self, emitter, bufs, event):
+        self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
+
+    def ready(self) -> bool:
+        return self._value is not None or self._event.query()
+
+    def result(self):
+        """-> (samples float32 numpy [rec[0]], SOLA offset, head offset)"""
+        if self._value is None:
+            self._event.synchronize()
+            host = self._bufs[1]
+            n_out, k, h, _ = host[:4].view(torch.int32).tolist()
+            self._value = (host[4: 4 + n_out].numpy().copy(), k, h)
+            self._emitter._free.append(self._bufs)
+            self._bufs = None
+        return self._value
+
+
+class ChunkEmitter:
+    """ChunkSplicer plus the host rules of TTS.infer_stream behind it (head trim on a segment's first chunk, the mute behind its
+    last), for a loop that serves many streams and may not wait: push() enqueues one library call (`gsv_stream_emit`: the device
+    decides offset, head trim and length) and ONE asynchronous copy of the samples with their record into pinned memory, and
+    returns a handle.  Owns two tails used in turn (the call reads one and writes the other) and a pinned buffer per chunk in
+    flight, reused once its handle has been read.  `new_segment()` forgets the tail."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320):
+        self.overlap, self.search_len = int(overlap_samples), int(search_len)
+        self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
+        self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
+
+    def new_segment(self):
+        self._cur = None
+
+    def _buffers(self, need, device):
+        for j, b in enumerate(self._free):
+            if b[0].numel() >= need:
+                return self._free.pop(j)
+        cap = max(need, 1 << 14)
+        return (torch.empty(cap, dtype=torch.float32, device=device), torch.empty(cap, dtype=torch.float32).pin_memory())
+
+    def push(self, chunk: torch.Tensor, is_final: bool, trim_head: bool = False, mute_samples: int = 0) -> _Emitted:
+        if not chunk.is_cuda:
+            raise RuntimeError("the streaming splice runs on the HIP device only (no CPU fallback)")
+        L = N.lib()
+        x = chunk.to(torch.float32).reshape(-1).contiguous()
+        n, dev = int(x.numel()), x.device
+        if self._tails is None:
+            self._tails = torch.zeros(2, max(1, self.overlap), dtype=torch.float32, device=dev)
+            self._ws = torch.empty(L.gsv_stream_emit_workspace(self.search_len, n), dtype=torch.uint8, device=dev)   # the scores: any n
+        prev = None if self._cur is None else self._tails[self._cur]
+        nxt = 0 if self._cur is None else self._cur ^ 1
+        dbuf, hbuf = bufs = self._buffers(4 + n + int(mute_samples), dev)
+        N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
+                                  int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
+                                  self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                  N.current_stream_ptr(dev)))
+        self._cur = nxt
+        used = 4 + n + int(mute_samples)
+        hbuf[:used].copy_(dbuf[:used], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        return _Emitted(self, bufs, ev)

@@ -638,6 +638,30 @@ class Text2SemanticDecoder:
                 self._in_step_stream = False
                 cur.wait_stream(self._step_stream)
             return out
+        begun = self._begin_batched(x, y, bert_feature, top_k, top_p, temperature, generator, source, slots, async_refill)
+        if begun is None:
+            return [], torch.zeros(0, dtype=torch.int64, device=self.device)
+        batch_size, first, nxt, exhausted, bucket_i, mode, _ = begun
+        if not async_refill:
+            return SL.reference_order(self, x, y, bert_feature, batch_size, first, nxt, exhausted, bucket_i, check_interval,
+                                      on_finish, max_new_tokens, mode)
+        try:
+            pred, orig = self._async_loop(x, y, bert_feature, begun, check_interval, on_finish, max_new_tokens).run()
+            return pred, torch.tensor(orig, device=self.device)
+        finally:    # also on an exception (a prompt that does not fit): no prompt pass may outlive the call
+            if self._refill_stream is not None:
+                self._refill_stream.synchronize()
+
+    def _async_loop(self, x, y, bert_feature, begun, check_interval, on_finish, max_new_tokens):
+        batch_size, first, nxt, exhausted, _, mode, first_len = begun
+        loop = SL.AheadLoop if self.refill_ahead > 0 else SL.StagedLoop
+        return loop(self, x, y, bert_feature, batch_size, first, nxt, exhausted, first_len, check_interval, on_finish,
+                    max_new_tokens, mode == 2)
+
+    def _begin_batched(self, x, y, bert_feature, top_k, top_p, temperature, generator, source, slots, async_refill):
+        """a batched call up to its first window: the slot family, the control words, the first requests' prompt pass -> None
+        (no request) or (slots, first requests, next-request function, queue exhausted, bucket the prompt pass chose, sampling
+        mode, the first requests' prompt lengths)"""
         B = len(x)
         sizes = sorted(self.cuda_graph_buckets)
         if slots is not None:
@@ -668,7 +692,7 @@ class Text2SemanticDecoder:
         actual = len(first)
         dev = self.device
         if actual == 0:
-            return [], torch.zeros(0, dtype=torch.int64, device=dev)
+            return None
         if self._samp is None:
             mode, seed = self._sampling_mode(top_k, top_p, generator)
         else:       # ctl[0] = 2 if any request samples (it gates the fused token step); the call's seed is drawn as a scalar call draws it
@@ -698,15 +722,47 @@ class Text2SemanticDecoder:
         if mode == 2:       # device sampling: the noise stream of a slot is its REQUEST (placement-invariant samples)
             rt["tok_override"].zero_()
             rt["tok_override"][:actual] = torch.tensor([self._stream_id(c) for c in first], dtype=torch.int64, device=dev)
-        if not async_refill:
-            return SL.reference_order(self, x, y, bert_feature, batch_size, first, nxt, exhausted, bucket_i, check_interval,
-                                      on_finish, max_new_tokens, mode)
+        return batch_size, first, nxt, exhausted, bucket_i, mode, [int(a) + int(b) for a, b in zip(x_lens_h, y_lens_h)]
+
+    def infer_stream_batched(self, x: List[torch.Tensor], y: List[torch.Tensor], bert_feature: List[torch.Tensor],
+                             stream_chunk: int = 25, boost_first_chunk=True, slots: int = None, top_k=15, top_p=1.0,
+                             temperature=1.0, repetition_penalty=1.35, initial_suppression_steps=10, seed=None,
+                             max_new_tokens=None, check_interval: int = 5, generator=None, ticks: bool = False):
+        """`infer_stream` for many requests at once, on the slots of `infer_batched`'s asynchronous loop: a generator of
+        (request index, cumulative tokens int64 [1,1,n] on the device, is_final).  Requests interleave as their chunks become
+        known; there may be more requests than slots.
+
+        Per request the sequence is `infer_stream`'s for that request alone, given that it ends with an EOS: cumulative chunks
+        that lag one chunk behind, the first sent at once under `boost_first_chunk` (a bool, or one per request), the EOS in no
+        chunk, and a final chunk that starts with sample 0.  With top_k=1 in fp32 the tokens are equal too, whichever slot
+        decodes the request.  A request that ends at a full cache or at `max_new_tokens` ends with the tokens `infer_batched`
+        returns for it.  A slot's end shows one window late, so a chunk is known up to `check_interval` steps after its last token.
+
+        A scalar `repetition_penalty` applies to every request, as in `infer_stream` (`infer_batched` ignores a scalar); the
+        sampling arguments are scalars or one per request, as in `infer_batched`.  The loop runs on the caller's stream.
+        `ticks`: (None, None, False) is yielded behind every window too, for a caller that polls work of its own between windows.
+        Closing the generator waits for the prompt passes, parks the slots and unbinds the sampling table."""
+        n = len(x)
+        boost = [bool(b) for b in SS.per_request("boost_first_chunk", boost_first_chunk, n)]
+        if not SS.is_sequence(repetition_penalty):
+            repetition_penalty = [repetition_penalty] * n
+        if int(stream_chunk) < 1:
+            raise ValueError("stream_chunk must be positive, got %r" % (stream_chunk,))
+        self._samp = SS.resolve(n, top_k, top_p, temperature, seed, repetition_penalty, initial_suppression_steps)
+        loop = None
         try:
-            loop = SL.AheadLoop if self.refill_ahead > 0 else SL.StagedLoop
-            pred, orig = loop(self, x, y, bert_feature, batch_size, first, nxt, exhausted,
-                              [int(a) + int(b) for a, b in zip(x_lens_h, y_lens_h)], check_interval, on_finish, max_new_tokens,
-                              mode == 2).run()
-            return pred, torch.tensor(orig, device=dev)
-        finally:    # also on an exception (a prompt that does not fit): no prompt pass may outlive the call
+            with torch.inference_mode():
+                begun = self._begin_batched(x, y, bert_feature, 0, 1.0, 1.0, generator, None, slots, True)
+                if begun is not None:
+                    loop = self._async_loop(x, y, bert_feature, begun, check_interval, None, max_new_tokens)
+            if loop is not None:
+                for r, rows, is_final in SL.stream_chunks(loop, int(stream_chunk), boost, ticks):
+                    yield r, (None if rows is None else rows[None, None]), is_final
+        finally:
             if self._refill_stream is not None:
                 self._refill_stream.synchronize()
+            if loop is not None:
+                with torch.inference_mode():
+                    loop.stepped.rt["kv_len"].fill_(-1)
+            self._samp = None
+            self._unbind_sampling()

@@ -57,7 +57,7 @@ from . import slot_sampling
 from ._native import VOC_MAX_SEGMENTS
 from . import subtitles as sub
 from .batchmath import balance_order, per_text_values, split_bounds
-from .stream import ChunkSplicer
+from .stream import ChunkEmitter, ChunkSplicer
 from .loader import Gpt, Sovits, convert_to_safetensors, get_gpt_weights, get_sovits_weights
 
 log = logging.getLogger("gsv_tts_lite_amd")
@@ -170,6 +170,26 @@ class _EngineLock:
         self._owner = None
         self._lock.release()
         return False
+
+
+class _TextLine:
+    """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
+    local variables and in `vq.enc_p.y_overlap`, per text."""
+
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator):
+        self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
+        self.cut_mute, self.generator = cut_mute, generator
+        self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
+        self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
+        self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
+        self.emitter = ChunkEmitter(overlap_samples)
+        self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
+        self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
+        self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
+
+    @property
+    def done(self):
+        return self.seg >= len(self.cuts)
 
 
 class TTS:
@@ -962,6 +982,212 @@ class TTS:
                 except Exception:
                     pass
                 self._empty_cache()
+
+    def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
+                             is_cut_text=True, cut_minlen=10, cut_mute=0.4,
+                             cut_mute_scale_map={"…": 2.0, ".": 1.5, "。": 1.5, "?": 1.5, "？": 1.5, "!": 1.5, "！": 1.5,
+                                                 ",": 1.0, "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0,
+                                                 "、": 0.8, "・": 0.8},
+                             stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
+                             temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
+                             sovits_model=None, debug=True, slots=None, seed=None):
+        """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
+        `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
+        requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
+
+        Every segment `cut_text` makes of every text is a request of the continuous-batching slots
+        (Text2SemanticDecoder.infer_stream_batched), queued as segment 0 of each text, then segment 1, ...; `slots` names the
+        slot family (default: the smallest that holds them, else the largest).  The vocoder side of a text is sequential: its
+        chunks are decoded in order with the text's own overlap state, a later segment's chunks wait as token tensors until the
+        final clip of the segment before has been handed out.  What follows a chunk's decode runs on the device
+        (stream.ChunkEmitter); the samples -- and with return_subtitles the frame-to-phoneme path -- reach the host by an
+        asynchronous copy into pinned memory that is polled behind every window, so the
+        loop waits for nothing but the slots' own read-back while a slot is live.
+
+        top_k / top_p / temperature / seed / speed / noise_scale: one value or one per text.  With a seed, a text's vocoder noise
+        is drawn from a generator seeded with it: the text's audio does not depend on its neighbours.  The speaker and the
+        prompt are broadcast as in `infer_batched`.  Not available under a multi-rank engine."""
+        with self._infer_lock:
+            vq, gen = None, None
+            try:
+                if isinstance(texts, str):
+                    texts = [texts]
+                n = len(texts)
+                if n == 0:
+                    return
+                speed = slot_sampling.per_request("speed", speed, n)
+                noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
+                if not all(s > 0 for s in speed):
+                    raise ValueError("speed must be positive, got %r" % (speed,))
+                if any(self._contains_chinese(t) for t in texts):
+                    self._ensure_bert_loaded()
+                texts = [t if self._check_pause(t) else t + "." for t in texts]
+                if stream_mode == "sentence":
+                    stream_chunk = 10000
+                if not is_cut_text:
+                    cut_minlen = 10000
+                bc = lambda v, kinds: [v] * n if isinstance(v, kinds) else list(v)
+                spk_audio_paths = bc(spk_audio_paths, (str, dict))
+                prompt_audio_paths = bc(prompt_audio_paths, str)
+                prompt_audio_texts = bc(prompt_audio_texts, str)
+                gpt_model = self._pick(self.gpt_models, gpt_model, self.default_gpt_path)
+                sovits_model = self._pick(self.sovits_models, sovits_model, self.default_sovits_path)
+                if gpt_model not in self.gpt_models:
+                    self.load_gpt_model(gpt_model)
+                if sovits_model not in self.sovits_models:
+                    self.load_sovits_model(sovits_model)
+                t2s = self.gpt_models[gpt_model].t2s_model
+                vq = self.sovits_models[sovits_model].vq_model
+                if self._engine(t2s) is not None:
+                    raise NotImplementedError("infer_stream_batched runs in a single process: multi-GPU streaming is not built")
+                dev = self.tts_config.device
+                seeds = slot_sampling.per_request("seed", seed, n)
+                lines = []
+                for t, text in enumerate(texts):
+                    gen_t = None if seeds[t] is None else torch.Generator().manual_seed(int(seeds[t]))
+                    lines.append(_TextLine(text, cut_text(text, cut_minlen), self._ge_for(spk_audio_paths[t], sovits_model),
+                                           overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t))
+                # the queue: segment 0 of every text, then segment 1, ...
+                req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
+                seg2orig = [t for t, _ in req]
+                ids, prompts, berts = [], [], []
+                for t, j in req:
+                    phones2, word2ph, bert2, norm_text = self._phones_and_bert(lines[t].cuts[j])
+                    prompt, ph1, b1 = self._prompt_for(prompt_audio_paths[t], prompt_audio_texts[t])
+                    ids.append(torch.tensor(ph1 + phones2, dtype=torch.int64, device=dev))
+                    prompts.append(prompt.squeeze(0))
+                    berts.append(torch.cat([b1, bert2]))
+                    lines[t].segs.append((torch.tensor(phones2, dtype=torch.int64, device=dev).unsqueeze(0), word2ph, norm_text))
+                sampling = {k: slot_sampling.per_segment(k, v, n, seg2orig) for k, v in
+                            (("top_k", top_k), ("top_p", top_p), ("temperature", temperature), ("seed", seed),
+                             ("repetition_penalty", repetition_penalty))}
+                boost = slot_sampling.per_request("boost_first_chunk", boost_first_chunk, n)
+                gen = t2s.infer_stream_batched(ids, prompts, berts, stream_chunk=stream_chunk,
+                                               boost_first_chunk=[bool(boost[t]) and j == 0 for t, j in req], slots=slots,
+                                               ticks=True, **sampling)
+                mute = lambda ln, cut: self._stream_mute(ln.cut_mute, cut, cut_mute_scale_map)
+                for r, pred, is_final in gen:       # one turn per window of the slot loop
+                    if r is not None:
+                        t, j = req[r]
+                        lines[t].waiting[j].append((pred, is_final))
+                    for t, ln in enumerate(lines):
+                        self._stream_decode(ln, vq, overlap_len, return_subtitles, mute)
+                        while ln.in_flight and ln.in_flight[0][0].ready():
+                            yield t, self._stream_clip(ln, mute)
+                gen = None
+                while any(not ln.done for ln in lines):      # no slot is live: what is left is waited for, text by text in turn
+                    moved = False
+                    for t, ln in enumerate(lines):
+                        self._stream_decode(ln, vq, overlap_len, return_subtitles, mute)
+                        if ln.in_flight:
+                            moved = True
+                            yield t, self._stream_clip(ln, mute)
+                    if not moved:
+                        raise RuntimeError("infer_stream_batched: a segment ended without its final chunk")
+            finally:
+                if gen is not None:
+                    gen.close()         # waits for the refill stream, parks the slots
+                if vq is not None and vq.enc_p is not None:
+                    vq.enc_p.y_overlap = None
+                self._empty_cache()
+
+    def _stream_mute(self, cut_mute, text_cut, scale_map):
+        """seconds of silence behind a segment's final chunk (TTS.py:456-462)"""
+        if text_cut[-1] in scale_map:
+            return cut_mute * scale_map[text_cut[-1]]
+        if "…" in scale_map and text_cut[-3:] in ["...", "。。。"]:
+            return cut_mute * scale_map["…"]
+        return cut_mute * 1.0
+
+    def _stream_decode(self, ln, vq, overlap_len, return_subtitles, mute):
+        """enqueue the vocoder pass and the epilogue of every chunk of the text's current segment that has its tokens"""
+        while not ln.done and ln.waiting[ln.seg] and not ln.final_issued:
+            pred, is_final = ln.waiting[ln.seg].pop(0)
+            phones2_t = ln.segs[ln.seg][0]
+            with torch.inference_mode():
+                vq.enc_p.y_overlap = ln.y_overlap       # the text's own cross-fade state goes through the holder decode() reads
+                try:
+                    audio, attn = vq.decode(pred, phones2_t, ln.ge, noise_scale=ln.noise_scale, speed=ln.speed, stream_mode=True,
+                                            valid_start_idx=ln.valid_start_idx, overlap_len=overlap_len, generator=ln.generator)
+                    ln.y_overlap = vq.enc_p.y_overlap
+                finally:
+                    vq.enc_p.y_overlap = None
+                if not is_final:
+                    attn = attn[:, :-overlap_len, :]
+                    ln.valid_start_idx = attn.shape[1]
+                assign = None
+                if return_subtitles:
+                    # the frame -> phoneme path goes to the host the way the samples go: an asynchronous copy into pinned memory,
+                    # queued in front of the emitter's copy on the same stream, so the handle's event covers both
+                    path = sub.viterbi_monotonic(attn)
+                    assign = torch.empty(path.shape, dtype=path.dtype, pin_memory=True)
+                    assign.copy_(path, non_blocking=True)
+                first = ln.chunk_idx == 0
+                if first:
+                    ln.emitter.new_segment()
+                n_mute = int(mute(ln, ln.cuts[ln.seg]) * self.samplerate) if is_final else 0
+                handle = ln.emitter.push(audio, is_final, trim_head=first, mute_samples=n_mute)
+            ln.in_flight.append((handle, assign, is_final, first))
+            ln.chunk_idx += 1
+            ln.final_issued = is_final
+
+    def _stream_clip(self, ln, mute):
+        """the oldest chunk in flight of a text as its AudioClip (waits for its copy): the host rules of infer_stream behind the
+        samples -- subtitles, audio_len_s -- with the head offset the device chose.  `assign` is on the host by then (its copy was
+        queued before the samples'), so nothing here reads the device"""
+        handle, assign, is_final, first = ln.in_flight.pop(0)
+        audio, _, head = handle.result()
+        if first:
+            ln.head_offset = head
+        text_cut = ln.cuts[ln.seg]
+        _, word2ph, norm_text = ln.segs[ln.seg]
+        subtitles = []
+        if assign is not None and (is_final or sub.is_normal_assign(assign)):
+            subtitles = sub.get_subtitles(word2ph, assign, ln.speed, last_end_s=ln.last_end_s, sovits_hz=self.sovits_hz)
+        if subtitles:
+            sub.increment_subtitle_times(subtitles, -ln.head_offset / self.samplerate)
+            subtitles[0]["start_s"] = max(ln.last_end_s, subtitles[0]["start_s"])
+        if is_final and subtitles:
+            self._close_subtitles(subtitles, word2ph, mute(ln, text_cut))
+            ln.last_end_s = subtitles[-1]["end_s"]
+        new_subtitles = []
+        if subtitles:
+            subtitles = sub.sub2text_index(subtitles, norm_text, text_cut)
+            sub.increment_subtitle_indices(subtitles, ln.cur_text_l)
+            new_subtitles = subtitles[ln.last_subtitles_end:]
+            ln.last_subtitles_end = len(subtitles) - 1
+            if not is_final and new_subtitles:
+                new_subtitles[-1]["end_s"] = None
+        ln.audio_len_s += len(audio) / self.samplerate
+        if is_final:        # the next segment starts clean (TTS.py:498): its chunks may be decoded from now on
+            ln.cur_text_l += len(text_cut)
+            ln.seg, ln.y_overlap, ln.valid_start_idx, ln.chunk_idx, ln.last_subtitles_end = ln.seg + 1, None, 0, 0, 0
+            ln.final_issued = False
+        return AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
+
+    async def infer_stream_batched_async(self, *args, executor=None, **kwargs):
+        """async generator of (text index, AudioClip): infer_stream_batched in an executor thread, handed over a queue"""
+        import asyncio
+        loop = asyncio.get_running_loop()
+        queue = asyncio.Queue()
+        failure = []
+
+        def pump():
+            try:
+                for item in self.infer_stream_batched(*args, **kwargs):
+                    loop.call_soon_threadsafe(queue.put_nowait, item)
+            except BaseException as exc:
+                failure.append(exc)
+            finally:
+                loop.call_soon_threadsafe(queue.put_nowait, None)
+        loop.run_in_executor(executor, pump)
+        while True:
+            item = await queue.get()
+            if item is None:
+                break
+            yield item
+        if failure:
+            raise failure[0]
 
     @torch.inference_mode()
     def infer_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,

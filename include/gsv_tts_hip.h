@@ -405,6 +405,27 @@ size_t gsv_sola_workspace(int search_len);
 int gsv_sola(const float* prev_tail, const float* chunk, int n, int overlap, int search_len, float* out, int32_t* offset,
              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Chunk epilogue of a stream: everything TTS.infer_stream does between the decode of a chunk and its hand-out (TTS.py:429-470: the
+ * splice above, the tail kept back, the head trim of TTS._find_head_threshold_offsets on a segment's first chunk, the mute behind its
+ * last), in that order, with no value read by the host in between -- many streams can be served from one loop.
+ *   prev_tail fp32 [overlap] or NULL (first chunk of a segment: offset 0, no cross-fade); chunk fp32 [n], n >= overlap.
+ *   k: gsv_sola's offset; s: gsv_sola's spliced signal, m = n - k samples, bit for bit.
+ *   tail_out fp32 [overlap] = s[m - overlap : m]; it must not alias prev_tail (keep two tails and use them in turn).
+ *   body = s if is_final, else s[: m - overlap].
+ *   h = 0 unless trim_head: over the first L = min(len(body), 64000) samples of body, in frames of 512 with hop 256, the first
+ *   frame f with sqrtf(sum of squares / 512) > 0.02f gives h = max(0, 256 f - 3200); no such frame, or L < 512: h = L.  The fp32 sum
+ *   of a frame is H[f] + H[f + 1]; H[j], over the 256 samples from 256 j, is taken by 64 lanes: lane l adds s[256 j + l + 64 t]^2 for
+ *   t = 0..3 in that order (fused multiply-add), then the lanes are added pairwise at strides 32, 16, 8, 4, 2, 1.
+ *   -> out fp32 (capacity n + mute_samples) = body[h:], followed by mute_samples zeros if is_final;
+ *      rec int32 [4] (device) = {samples written to out, k, h, 0}: copy it with `out` behind the stream.
+ *   workspace: gsv_stream_emit_workspace(search_len, n) bytes, device (0: a negative argument).  Three launches (score -- with a tail
+ *   only --, decide, copy), nothing allocated, nothing read by the host.  GSV_ERR_ARG: n < overlap, a negative size, overlap < 1 with a
+ *   tail, tail_out == prev_tail, or a workspace that is too small. */
+size_t gsv_stream_emit_workspace(int search_len, int n);
+int gsv_stream_emit(const float* prev_tail, const float* chunk, int n, int overlap, int search_len, int is_final, int trim_head,
+                    int mute_samples, float* out, float* tail_out, int32_t* rec, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
