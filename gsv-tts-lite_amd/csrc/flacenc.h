@@ -209,7 +209,7 @@ inline uint32_t flac_encode_frame_host(const float* x, int n, int bits, const ui
     return w.at + 2;
 }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(GSV_FLACENC_NO_KERNEL)   // track.h wants the scalar pieces only
 // ------------------------------------------------------------------------------------------------------------------
 // the device encoder: one wave of 64 lanes per frame, one frame per block
 // ------------------------------------------------------------------------------------------------------------------

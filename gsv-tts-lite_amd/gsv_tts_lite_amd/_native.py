@@ -36,6 +36,7 @@ EXPORTS = [
     "gsv_wav_to_mono", "gsv_wav_to_mono_batch",
     "gsv_flac_decode_workspace", "gsv_flac_decode", "gsv_flac_decode_host",
     "gsv_flac_encode_bound", "gsv_flac_encode_workspace", "gsv_flac_encode", "gsv_flac_encode_host",
+    "gsv_track_state_bytes", "gsv_track_out_capacity", "gsv_track_init", "gsv_track_push", "gsv_track_init_host", "gsv_track_push_host",
 ]
 
 
@@ -248,6 +249,10 @@ def lib():
         "gsv_flac_decode_host": [vp, sz, ctypes.POINTER(FlacClip), i, ctypes.POINTER(FlacFrame), i, vp, vp],
         "gsv_flac_encode": [vp, sz, ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i, vp, sz, vp, vp, vp, sz, vp],
         "gsv_flac_encode_host": [vp, sz, ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i, vp, sz, vp, vp],
+        "gsv_track_init": [vp, sz, i, i, i, i, vp],
+        "gsv_track_push": [vp, vp, i, vp, i, vp, vp, vp],
+        "gsv_track_init_host": [vp, sz, i, i, i, i],
+        "gsv_track_push_host": [vp, vp, i, vp, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -284,6 +289,10 @@ def lib():
     for fn in (L.gsv_flac_encode_bound, L.gsv_flac_encode_workspace):
         fn.argtypes = [ctypes.POINTER(FlacEncClip), i, ctypes.POINTER(FlacEncFrame), i]
         fn.restype = sz
+    L.gsv_track_state_bytes.argtypes = [i, i, i, i]
+    L.gsv_track_state_bytes.restype = sz
+    L.gsv_track_out_capacity.argtypes = [i, i, i, i, i]
+    L.gsv_track_out_capacity.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

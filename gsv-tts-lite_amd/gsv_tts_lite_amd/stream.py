@@ -8,7 +8,9 @@ compute on this path and no CPU fallback.
 
 `ChunkEmitter` is the same splice for a loop that serves many streams (TTS.infer_stream_batched) and may not wait for the device:
 `gsv_stream_emit` also trims the head of a segment's first chunk and appends the mute behind its last, decides the chunk's length on
-the device, and the samples reach the host by one asynchronous copy behind a handle."""
+the device, and the samples reach the host by one asynchronous copy behind a handle.  With a `track` (track.TrackResampler) the s16
+packets of a real-time track are made behind it by `gsv_track_push`, which reads the chunk's length from the emit record on the
+device, and travel in the same copy."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -56,19 +58,26 @@ class ChunkSplicer:
 class _Emitted:
     """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
 
-    def __init__(self, emitter, bufs, event):
+    def __init__(self, emitter, bufs, event, pcm_at=None):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
+        self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
 
     def ready(self) -> bool:
         return self._value is not None or self._event.query()
 
     def result(self):
-        """-> (samples float32 numpy [rec[0]], SOLA offset, head offset)"""
+        """-> (samples float32 numpy [rec[0]], SOLA offset, head offset); with a track also its packets, int16 numpy
+        [packets, packet * channels]"""
         if self._value is None:
             self._event.synchronize()
             host = self._bufs[1]
             n_out, k, h, _ = host[:4].view(torch.int32).tolist()
             self._value = (host[4: 4 + n_out].numpy().copy(), k, h)
+            if self._pcm_at is not None:
+                fmt = self._emitter.track.fmt
+                packets = int(host[self._pcm_at: self._pcm_at + 4].view(torch.int32)[0])
+                pcm = host[self._pcm_at + 4:].view(torch.int16)[: packets * fmt.packet * fmt.channels]
+                self._value += (pcm.numpy().copy().reshape(packets, fmt.packet * fmt.channels),)
             self._emitter._free.append(self._bufs)
             self._bufs = None
         return self._value
@@ -79,10 +88,15 @@ class ChunkEmitter:
     last), for a loop that serves many streams and may not wait: push() enqueues one library call (`gsv_stream_emit`: the device
     decides offset, head trim and length) and ONE asynchronous copy of the samples with their record into pinned memory, and
     returns a handle.  Owns two tails used in turn (the call reads one and writes the other) and a pinned buffer per chunk in
-    flight, reused once its handle has been read.  `new_segment()` forgets the tail."""
+    flight, reused once its handle has been read.  `new_segment()` forgets the tail.
 
-    def __init__(self, overlap_samples: int, search_len: int = 320):
-        self.overlap, self.search_len = int(overlap_samples), int(search_len)
+    track: a track.TrackResampler on the chunks' device, or None.  With one, push() also enqueues `gsv_track_push` over the samples
+    `gsv_stream_emit` wrote, their number read from its record on the device, and the packets with their record ride behind the
+    samples in the same buffer and the same copy; `flush` ends the track's stream (the last chunk of a text).  The track's state
+    outlives `new_segment()`: one stream spans a text's segments and the mutes between them."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320, track=None):
+        self.overlap, self.search_len, self.track = int(overlap_samples), int(search_len), track
         self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
         self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
 
@@ -96,7 +110,7 @@ class ChunkEmitter:
         cap = max(need, 1 << 14)
         return (torch.empty(cap, dtype=torch.float32, device=device), torch.empty(cap, dtype=torch.float32).pin_memory())
 
-    def push(self, chunk: torch.Tensor, is_final: bool, trim_head: bool = False, mute_samples: int = 0) -> _Emitted:
+    def push(self, chunk: torch.Tensor, is_final: bool, trim_head: bool = False, mute_samples: int = 0, flush: bool = False) -> _Emitted:
         if not chunk.is_cuda:
             raise RuntimeError("the streaming splice runs on the HIP device only (no CPU fallback)")
         L = N.lib()
@@ -107,14 +121,20 @@ class ChunkEmitter:
             self._ws = torch.empty(L.gsv_stream_emit_workspace(self.search_len, n), dtype=torch.uint8, device=dev)   # the scores: any n
         prev = None if self._cur is None else self._tails[self._cur]
         nxt = 0 if self._cur is None else self._cur ^ 1
-        dbuf, hbuf = bufs = self._buffers(4 + n + int(mute_samples), dev)
+        used = 4 + n + int(mute_samples)
+        pcm_cap = 0 if self.track is None else (self.track.capacity(used - 4) + 1) // 2      # int16 pairs as fp32 elements
+        dbuf, hbuf = bufs = self._buffers(used + (0 if self.track is None else 4 + pcm_cap), dev)
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
                                   int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
                                   self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        used = 4 + n + int(mute_samples)
+        pcm_at = None
+        if self.track is not None:       # [rec 4 | samples | track rec 4 | packets], all in fp32 elements
+            pcm_at = used
+            self.track.enqueue(dbuf[4:].data_ptr(), used - 4, dbuf.data_ptr(), flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
+            used += 4 + pcm_cap
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev)
+        return _Emitted(self, bufs, ev, pcm_at)

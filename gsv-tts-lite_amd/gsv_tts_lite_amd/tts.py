@@ -58,6 +58,7 @@ from ._native import VOC_MAX_SEGMENTS
 from . import subtitles as sub
 from .batchmath import balance_order, per_text_values, split_bounds
 from .stream import ChunkEmitter, ChunkSplicer
+from .track import TrackFormat, TrackResampler
 from .loader import Gpt, Sovits, convert_to_safetensors, get_gpt_weights, get_sovits_weights
 
 log = logging.getLogger("gsv_tts_lite_amd")
@@ -92,6 +93,8 @@ class AudioClip:
         self.audio_len_s = audio_len_s
         self.subtitles = subtitles
         self.orig_text = orig_text
+        self.pcm = None             # a stream with track=: int16 [k, packet * channels], the whole packets this clip completed
+        self.pcm_rate = None        # and the track's sample rate
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -119,6 +122,13 @@ class AudioClip:
         server that returns the file in a response: what save("x.flac") writes, without the file"""
         from . import flacio
         return flacio.encode_flac(self.audio_data, self.samplerate, bits=bits)
+
+    def to_pcm16(self, rate: int = 48000, channels: int = 1, packet_ms=20) -> np.ndarray:
+        """the clip as the packets of a real-time track (track.pcm16): int16 [k, packet * channels] at `rate`, the last packet
+        filled with zeros.  What a stream with track=TrackFormat(rate, channels, packet_ms) carries in its clips' `pcm`, all
+        clips of a text together, bit for bit."""
+        from . import track
+        return track.pcm16(self.audio_data, self.samplerate, track.TrackFormat(rate, channels, packet_ms))
 
     def _save_wav(self, save_path):
         import wave
@@ -176,13 +186,13 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        self.emitter = ChunkEmitter(overlap_samples)
+        self.emitter = ChunkEmitter(overlap_samples, track=track)        # track: the text's own TrackResampler, or None
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
         self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
@@ -895,11 +905,16 @@ class TTS:
                                          "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0, "、": 0.8, "・": 0.8},
                      stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                      temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                     sovits_model=None, debug=True):
+                     sovits_model=None, debug=True, track=None):
         """TTS.py:289-504: generator of AudioClip chunks.  Per text segment the GPT streams cumulative token
         chunks (t2s.infer_stream); every chunk is decoded from the start of the segment with
         decode(stream_mode=True) -- only frames past `valid_start_idx` reach the flow / Generator -- and joined
-        to the previous one by SOLA over `overlap_len` frames."""
+        to the previous one by SOLA over `overlap_len` frames.
+
+        track: a track.TrackFormat, or None.  With one, every clip also carries `pcm` -- int16 [k, packet * channels], the whole
+        packets of a real-time track at `pcm_rate` that its samples completed (k may be 0) --: one resampler state spans the
+        text, its segments and the mutes between them, and the text's final clip flushes it.  The concatenated `pcm` is
+        AudioClip.to_pcm16 of the concatenated audio_data, bit for bit.  Nothing else about the clips changes."""
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -924,7 +939,9 @@ class TTS:
                 prompt, phones1, bert1 = self._prompt_for(prompt_audio_path, prompt_audio_text)
                 overlap_samples = overlap_len * vq.samples_per_frame
                 audio_len_s, cur_text_l, last_end_s = 0.0, 0, 0
-                for i, text_cut in enumerate(cut_text(text, cut_minlen)):
+                cuts = cut_text(text, cut_minlen)
+                resampler = None if track is None else TrackResampler(track, self.samplerate, dev)
+                for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
                     bert = torch.cat([bert1, bert2]).unsqueeze(0)
@@ -970,9 +987,13 @@ class TTS:
                                 last_subtitles_end = len(subtitles) - 1
                                 if not is_final and new_subtitles:
                                     new_subtitles[-1]["end_s"] = None
+                            pcm = None if resampler is None else resampler.push(audio, flush=is_final and i == len(cuts) - 1)
                             audio = audio.float().cpu().numpy()
                         audio_len_s += len(audio) / self.samplerate
-                        yield AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
+                        clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
+                        if resampler is not None:
+                            clip.pcm, clip.pcm_rate = pcm, track.rate
+                        yield clip
                         chunk_idx += 1
                     vq.enc_p.y_overlap = None
                     cur_text_l += len(text_cut)
@@ -990,7 +1011,7 @@ class TTS:
                                                  "、": 0.8, "・": 0.8},
                              stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                              temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                             sovits_model=None, debug=True, slots=None, seed=None):
+                             sovits_model=None, debug=True, slots=None, seed=None, track=None):
         """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
         `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
         requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
@@ -1006,7 +1027,10 @@ class TTS:
 
         top_k / top_p / temperature / seed / speed / noise_scale: one value or one per text.  With a seed, a text's vocoder noise
         is drawn from a generator seeded with it: the text's audio does not depend on its neighbours.  The speaker and the
-        prompt are broadcast as in `infer_batched`.  Not available under a multi-rank engine."""
+        prompt are broadcast as in `infer_batched`.  Not available under a multi-rank engine.
+
+        track: as in `infer_stream`; every text has its own resampler state, and its push is enqueued behind the chunk's epilogue
+        with the chunk's length read on the device, so the loop still waits for nothing."""
         with self._infer_lock:
             vq, gen = None, None
             try:
@@ -1046,7 +1070,8 @@ class TTS:
                 for t, text in enumerate(texts):
                     gen_t = None if seeds[t] is None else torch.Generator().manual_seed(int(seeds[t]))
                     lines.append(_TextLine(text, cut_text(text, cut_minlen), self._ge_for(spk_audio_paths[t], sovits_model),
-                                           overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t))
+                                           overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t,
+                                           None if track is None else TrackResampler(track, self.samplerate, dev)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1126,7 +1151,8 @@ class TTS:
                 if first:
                     ln.emitter.new_segment()
                 n_mute = int(mute(ln, ln.cuts[ln.seg]) * self.samplerate) if is_final else 0
-                handle = ln.emitter.push(audio, is_final, trim_head=first, mute_samples=n_mute)
+                handle = ln.emitter.push(audio, is_final, trim_head=first, mute_samples=n_mute,
+                                         flush=is_final and ln.seg == len(ln.cuts) - 1)
             ln.in_flight.append((handle, assign, is_final, first))
             ln.chunk_idx += 1
             ln.final_issued = is_final
@@ -1136,7 +1162,7 @@ class TTS:
         samples -- subtitles, audio_len_s -- with the head offset the device chose.  `assign` is on the host by then (its copy was
         queued before the samples'), so nothing here reads the device"""
         handle, assign, is_final, first = ln.in_flight.pop(0)
-        audio, _, head = handle.result()
+        audio, _, head, *pcm = handle.result()
         if first:
             ln.head_offset = head
         text_cut = ln.cuts[ln.seg]
@@ -1163,7 +1189,10 @@ class TTS:
             ln.cur_text_l += len(text_cut)
             ln.seg, ln.y_overlap, ln.valid_start_idx, ln.chunk_idx, ln.last_subtitles_end = ln.seg + 1, None, 0, 0, 0
             ln.final_issued = False
-        return AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
+        clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
+        if pcm:
+            clip.pcm, clip.pcm_rate = pcm[0], ln.emitter.track.fmt.rate
+        return clip
 
     async def infer_stream_batched_async(self, *args, executor=None, **kwargs):
         """async generator of (text index, AudioClip): infer_stream_batched in an executor thread, handed over a queue"""

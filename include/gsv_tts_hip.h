@@ -426,6 +426,36 @@ int gsv_stream_emit(const float* prev_tail, const float* chunk, int n, int overl
                     int mute_samples, float* out, float* tail_out, int32_t* rec, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* Real-time track output: a stream of fp32 samples at in_rate -> s16 packets of `packet` samples per channel at out_rate,
+ * whatever the chunks the stream arrives in (csrc/track.h).  With the rates reduced by their gcd to o and w,
+ * width and L = 2 width + o as gsv_sv_resample has them and K torchaudio's sinc table (built on the HOST in fp64, cast to
+ * fp32 and uploaded, so device and host twin share its bits), a stream x[0, N) gives M = ceil(w N / o) outputs
+ *   y[j w + p] = sum_{i < L} x[j o - width + i] K[p][i]   (samples outside [0, N) skipped; fp32, tap order, fused multiply-add),
+ * y = x if o == w; q = the FLAC writer's quantiser at 16 bits (x 2^15, round half to even, clamp, NaN -> 0); with 2 channels
+ * every q is written twice, interleaved; the s16 stream is cut into packets, and a flush fills the last with zeros.
+ * After N_t samples the outputs that exist are the first min(w J, ceil(w N_t / o)), J = 0 if N_t < width + o, else
+ * (N_t - width - o) / o + 1 (N_t if o == w); a flush makes the rest up to M and returns the state to fresh.
+ *   state: caller-owned, gsv_track_state_bytes bytes (0: bad arguments -- packet 1..4096, channels 1 or 2, a rate pair
+ *   gsv_sv_resample accepts), 16-byte aligned, made by gsv_track_init: a header (samples in, outputs out, samples carried), the
+ *   table, a ring of the last L + o input samples, a carry of packet x channels int16.
+ *   gsv_track_out_capacity: the int16 elements a push of at most n_cap samples can write (what `out` must hold).
+ *   gsv_track_push: chunk fp32 [n_cap] (may be NULL when n_cap is 0); n_dev NULL or a device int32 holding the real length
+ *   (clamped to 0..n_cap) -- gsv_stream_emit's rec, so the call sits directly behind it --; out: whole packets, contiguous
+ *   (the samples of the next, partial packet lie behind them until the second launch has moved them to the carry);
+ *   rec int32 [4] (device) = {packets written, outputs produced by this call, samples per channel left in the carry, zeros
+ *   per channel padded by the flush}.  Two launches, nothing allocated, nothing read by the host.
+ *   gsv_track_init_host / gsv_track_push_host: the same over HOST memory from the same scalar routines -- the CPU path and
+ *   the device's oracle (device bytes equal host bytes); they need no GPU.
+ * GSV_ERR_ARG: a null pointer, a negative size, bad rates / packet / channels, a state that is too small or misaligned. */
+size_t gsv_track_state_bytes(int in_rate, int out_rate, int packet, int channels);
+size_t gsv_track_out_capacity(int n_cap, int in_rate, int out_rate, int packet, int channels);
+int gsv_track_init(void* state, size_t bytes, int in_rate, int out_rate, int packet, int channels, void* stream);
+int gsv_track_push(void* state, const float* chunk, int n_cap, const int32_t* n_dev, int flush, int16_t* out, int32_t* rec,
+                   void* stream);
+int gsv_track_init_host(void* state, size_t bytes, int in_rate, int out_rate, int packet, int channels);
+int gsv_track_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, int16_t* out,
+                        int32_t* rec);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
