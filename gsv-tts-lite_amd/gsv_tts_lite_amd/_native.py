@@ -37,6 +37,7 @@ EXPORTS = [
     "gsv_flac_decode_workspace", "gsv_flac_decode", "gsv_flac_decode_host",
     "gsv_flac_encode_bound", "gsv_flac_encode_workspace", "gsv_flac_encode", "gsv_flac_encode_host",
     "gsv_track_state_bytes", "gsv_track_out_capacity", "gsv_track_init", "gsv_track_push", "gsv_track_init_host", "gsv_track_push_host",
+    "gsv_loudness_work_bytes", "gsv_loudness", "gsv_loudness_host",
 ]
 
 
@@ -133,6 +134,19 @@ class FlacEncChoice(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint8), ("order", ctypes.c_uint8), ("porder", ctypes.c_uint8), ("method", ctypes.c_uint8),
                 ("k", ctypes.c_uint8 * 64)]
 
+
+class LoudnessClip(ctypes.Structure):
+    """gsv_loudness_clip: one clip of gsv_loudness; target NaN: measure only"""
+    _fields_ = [("offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("target", ctypes.c_float)]
+
+
+class LoudnessRecord(ctypes.Structure):
+    """gsv_loudness_record: what gsv_loudness found and did per clip"""
+    _fields_ = [("zbar", ctypes.c_double), ("gain", ctypes.c_float), ("peak", ctypes.c_float), ("blocks", ctypes.c_int32),
+                ("above_abs", ctypes.c_int32), ("kept", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+LOUD_LIMITED, LOUD_MEASURED, LOUD_NONFINITE = 1, 2, 4       # GSV_LOUD_*
 
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
@@ -253,6 +267,8 @@ def lib():
         "gsv_track_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_track_init_host": [vp, sz, i, i, i, i],
         "gsv_track_push_host": [vp, vp, i, vp, i, vp, vp],
+        "gsv_loudness": [vp, sz, ctypes.POINTER(LoudnessClip), i, i, ctypes.c_float, vp, vp, vp, sz, vp],
+        "gsv_loudness_host": [vp, sz, ctypes.POINTER(LoudnessClip), i, i, ctypes.c_float, vp, vp, vp, sz],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -293,6 +309,8 @@ def lib():
     L.gsv_track_state_bytes.restype = sz
     L.gsv_track_out_capacity.argtypes = [i, i, i, i, i]
     L.gsv_track_out_capacity.restype = sz
+    L.gsv_loudness_work_bytes.argtypes = [ctypes.POINTER(LoudnessClip), i, i]
+    L.gsv_loudness_work_bytes.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

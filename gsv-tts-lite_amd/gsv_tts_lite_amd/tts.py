@@ -95,6 +95,9 @@ class AudioClip:
         self.orig_text = orig_text
         self.pcm = None             # a stream with track=: int16 [k, packet * channels], the whole packets this clip completed
         self.pcm_rate = None        # and the track's sample rate
+        self.lufs = None            # a clip made with loudness= (or by normalised()): the integrated loudness before the gain,
+        self.gain = None            # the gain applied (np.float32: audio_data is the unnormalised samples times it)
+        self.limited = None         # and whether the peak limit, not the target, set that gain
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -130,12 +133,36 @@ class AudioClip:
         from . import track
         return track.pcm16(self.audio_data, self.samplerate, track.TrackFormat(rate, channels, packet_ms))
 
+    def loudness(self) -> float:
+        """ITU-R BS.1770 integrated loudness of audio_data in LUFS (loudness.integrated_loudness: measured on the GPU when there
+        is one, by the same arithmetic on the CPU otherwise); -inf for a clip with nothing to measure"""
+        from . import loudness
+        return loudness.integrated_loudness(self.audio_data, self.samplerate)
+
+    def normalised(self, target: float = -18.0, peak_limit: float = 1.0) -> "AudioClip":
+        """a new clip at `target` LUFS -- or as close as peak_limit lets its peak come --, same subtitles and text; its
+        lufs / gain / limited say what was measured and done (loudness.normalise)"""
+        from . import loudness
+        audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
+        return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text), rec)
+
     def _save_wav(self, save_path):
         import wave
         pcm = (np.clip(self.audio_data, -1.0, 1.0) * 32767.0).astype("<i2")
         with wave.open(save_path, "wb") as w:
             w.setnchannels(1); w.setsampwidth(2); w.setframerate(self.samplerate)
             w.writeframes(pcm.tobytes())
+
+
+def _with_loudness(clip, rec):
+    clip.lufs, clip.gain, clip.limited = rec.lufs, rec.gain, rec.limited
+    return clip
+
+
+def _check_loudness(v):
+    if v is not None and not np.isfinite(float(v)):
+        raise ValueError("loudness target %r" % (v,))
+    return None if v is None else float(v)
 
 
 def cut_text(text: str, minlen: int = 10) -> list:
@@ -779,7 +806,11 @@ class TTS:
     @torch.inference_mode()
     def infer(self, spk_audio_path, prompt_audio_path, prompt_audio_text, text, return_subtitles=False, top_k=15,
               top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-              sovits_model=None):
+              sovits_model=None, loudness=None):
+        """loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
+        peak rule, trailing 0.2 s of zeros included -- is measured and scaled to it on the device before the download
+        (loudness.py); the clip then carries lufs (before the gain), gain and limited."""
+        loudness = _check_loudness(loudness)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -815,6 +846,9 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
+                if loudness is not None:
+                    audio, rec = self._finish_on_device(audio.float(), loudness)
+                    return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text), rec)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -824,10 +858,28 @@ class TTS:
             finally:
                 self._empty_cache()
 
+    def _finish_on_device(self, audio, target):
+        """the tail of infer / infer_vc with loudness=: the peak rule (an IEEE division by max(peak, 1): dividing by 1 is exact, so
+        the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_loudness call
+        over the finished clip with its record written behind the samples: ONE download carries both -> (numpy samples, record)"""
+        from . import loudness as ld
+        if audio.numel():
+            audio = audio / audio.abs().max().clamp(min=1)
+        n = audio.numel() + int(0.2 * self.samplerate)
+        tail = (n + 1) // 2 * 2 - audio.numel() + ld.RECORD_BYTES // 4         # zeros to n, to an 8-byte boundary, the record
+        buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
+        rec = buf[buf.numel() - ld.RECORD_BYTES // 4:].view(torch.uint8)
+        ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0, buf[:n], rec)
+        host = buf.cpu().numpy()
+        return host[:n], ld.records(host[host.size - ld.RECORD_BYTES // 4:].view(np.uint8))[0]
+
     @torch.inference_mode()
-    def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None):
+    def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
+                 loudness=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
-        decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here)."""
+        decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
+        loudness: as in infer."""
+        loudness = _check_loudness(loudness)
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -844,10 +896,16 @@ class TTS:
                 phones, word2ph, _, norm_text = self._phones_and_bert(prompt_audio_text)
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
-                audio = audio[0, 0, :].float().cpu().numpy()
+                if loudness is not None:
+                    audio, rec = self._finish_on_device(audio[0, 0, :].float(), loudness)
+                else:
+                    audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
                 self._close_subtitles(subtitles, word2ph, 0.2)
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
+                if loudness is not None:
+                    return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
+                                                    prompt_audio_text), rec)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1226,7 +1284,7 @@ class TTS:
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
-                      initial_suppression_steps=0):
+                      initial_suppression_steps=0, loudness=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
 
@@ -1241,11 +1299,21 @@ class TTS:
         (SynthesizerTrn.decode_segments: no frame blends two utterances), the clips are cut at exact frame boundaries, the
         mute after a segment is cut_mute / speed of its text, and return_subtitles aligns each segment on its own block of
         the attention with its own speed; the last entry of a segment ends where that segment's audio ends.  A vocoder
-        batch then holds at most 64 segments (sovits_batch_size is capped there)."""
+        batch then holds at most 64 segments (sovits_batch_size is capped there).
+
+        loudness: None, a target in LUFS for every text, or one value or None per TEXT (a wrong length raises ValueError).  The
+        finished clips -- mutes between segments included -- of the texts with a value are measured and scaled in ONE packed
+        gsv_loudness call (loudness.py), on the gathering rank under a multi-rank engine; those clips carry lufs,
+        gain and limited.  A text with None comes back exactly as without the parameter."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
+                if loudness is not None:
+                    loudness = [_check_loudness(v) for v in (slot_sampling.per_request("loudness", loudness, len(texts))
+                                                             if slot_sampling.is_sequence(loudness) else [loudness] * len(texts))]
+                    if all(v is None for v in loudness):
+                        loudness = None
                 segmented = slot_sampling.is_sequence(speed) or slot_sampling.is_sequence(noise_scale)
                 if segmented:   # one value per text: the lengths are checked before any device work
                     speed = slot_sampling.per_request("speed", speed, len(texts))
@@ -1429,6 +1497,13 @@ class TTS:
                     a = np.concatenate(parts) if parts else np.zeros(0, np.float32)
                     subtitles = sub.cat_subtitles(*sparts) if return_subtitles else []
                     clips.append(AudioClip(self.audio_queue, a, self.samplerate, len(a) / self.samplerate, subtitles, t))
+                if loudness is not None:    # one packed call over the texts that asked
+                    from . import loudness as ld
+                    pick = [i for i, v in enumerate(loudness) if v is not None]
+                    scaled, recs = ld.normalise([clips[i].audio_data for i in pick], self.samplerate, [loudness[i] for i in pick], 1.0, device=dev)
+                    for i, a, rec in zip(pick, scaled, recs):
+                        clips[i].audio_data = a
+                        _with_loudness(clips[i], rec)
                 return tuple(clips)
             finally:
                 self._empty_cache()

@@ -456,6 +456,47 @@ int gsv_track_init_host(void* state, size_t bytes, int in_rate, int out_rate, in
 int gsv_track_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, int16_t* out,
                         int32_t* rec);
 
+/* Loudness: ITU-R BS.1770 integrated loudness (K-weighting, 400 ms blocks overlapping by 75 %, the absolute gate at -70 LUFS
+ * and the relative gate 10 LU under it) of n_clips clips of one packed fp32 buffer, and each clip scaled to its target
+ * (csrc/loudness.h).  The meter is the one pyloudnorm implements (its shelf design included), in fp64.
+ *   x: fp32 [n_x]; clip c is x[offset, offset + n_samples), mono at `rate` Hz (4000..768000); the clips do not overlap.
+ *   target: LUFS, NaN for a clip that is only measured.  peak_limit > 0: no gain lifts a clip's peak above it (inf: no limit).
+ *   out: NULL (measure only), x (in place) or a second buffer of n_x floats; only [offset, offset + n_samples) of each clip
+ *   is written: x * gain, one fp32 product (a gain of 1 copies the samples, and writes nothing in place).
+ *   records [n_clips]: zbar the mean square of the blocks past both gates -- the loudness is -0.691 + 10 log10(zbar) LUFS --,
+ *   the gain applied = min(sqrt(10^((target + 0.691) / 10) / zbar), peak_limit / peak) rounded to fp32 -- and, when the limit is
+ *   the smaller one and the fp32 product gain * peak would still round above peak_limit, one ulp less --, the input peak max|x|, the blocks,
+ *   those at or above the absolute gate, those past both gates, and flags.  A clip shorter than one block, a clip with no
+ *   block past the gates and a clip holding a NaN or an infinity (GSV_LOUD_NONFINITE) have no measurement: zbar 0, gain 1,
+ *   GSV_LOUD_MEASURED clear, samples unchanged.  The filtered signal is held as fp32, saturating: a finite sample so close to
+ *   FLT_MAX that the shelf lifts it past the fp32 range is measured at FLT_MAX (zbar and the gain stay finite).
+ *   work: caller-owned, gsv_loudness_work_bytes(clips, n_clips, rate) bytes (0: bad arguments), 16-byte aligned.
+ *   gsv_loudness: x, out, records and work are DEVICE memory, clips is HOST memory.  One small upload and at most seven launches
+ *   on `stream` (a clip longer than 16 384 samples is filtered in chunks side by side, their states chained); nothing allocated, nothing read back by the host.
+ *   gsv_loudness_host: the same over HOST memory from the same scalar routines -- the CPU path and the device's oracle
+ *   (device records and samples equal the host's bit for bit); it needs no GPU.
+ * GSV_ERR_ARG: a null pointer, a bad rate / peak_limit / clip count (1..65535), a clip outside [0, n_x), a workspace that
+ * is too small or misaligned. */
+typedef struct {
+    int64_t offset;         /* first sample of the clip in x */
+    int32_t n_samples;
+    float target;           /* LUFS; NaN: measure only */
+} gsv_loudness_clip;
+typedef struct {
+    double zbar;
+    float gain;
+    float peak;
+    int32_t blocks, above_abs, kept, flags;
+} gsv_loudness_record;
+#define GSV_LOUD_LIMITED 1      /* the peak limit was the smaller gain */
+#define GSV_LOUD_MEASURED 2
+#define GSV_LOUD_NONFINITE 4    /* a NaN or an infinity among the samples */
+size_t gsv_loudness_work_bytes(const gsv_loudness_clip* clips, int n_clips, int rate);
+int gsv_loudness(const float* x, size_t n_x, const gsv_loudness_clip* clips, int n_clips, int rate, float peak_limit, float* out,
+                 gsv_loudness_record* records, void* work, size_t work_bytes, void* stream);
+int gsv_loudness_host(const float* x, size_t n_x, const gsv_loudness_clip* clips, int n_clips, int rate, float peak_limit,
+                      float* out, gsv_loudness_record* records, void* work, size_t work_bytes);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
