@@ -38,6 +38,7 @@ EXPORTS = [
     "gsv_flac_encode_bound", "gsv_flac_encode_workspace", "gsv_flac_encode", "gsv_flac_encode_host",
     "gsv_track_state_bytes", "gsv_track_out_capacity", "gsv_track_init", "gsv_track_push", "gsv_track_init_host", "gsv_track_push_host",
     "gsv_loudness_work_bytes", "gsv_loudness", "gsv_loudness_host",
+    "gsv_level_state_bytes", "gsv_level_init", "gsv_level_push", "gsv_level_init_host", "gsv_level_push_host",
 ]
 
 
@@ -147,6 +148,15 @@ class LoudnessRecord(ctypes.Structure):
 
 
 LOUD_LIMITED, LOUD_MEASURED, LOUD_NONFINITE = 1, 2, 4       # GSV_LOUD_*
+
+
+class LevelRecord(ctypes.Structure):
+    """gsv_level_record: the running measure and the gains of one gsv_level_push"""
+    _fields_ = [("zbar", ctypes.c_double), ("gain_first", ctypes.c_float), ("gain_last", ctypes.c_float), ("clamped", ctypes.c_int64),
+                ("blocks", ctypes.c_int32), ("above_abs", ctypes.c_int32), ("kept", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+LEVEL_MEASURED, LEVEL_NONFINITE, LEVEL_FULL = 2, 4, 8       # GSV_LEVEL_*
 
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
@@ -269,6 +279,10 @@ def lib():
         "gsv_track_push_host": [vp, vp, i, vp, i, vp, vp],
         "gsv_loudness": [vp, sz, ctypes.POINTER(LoudnessClip), i, i, ctypes.c_float, vp, vp, vp, sz, vp],
         "gsv_loudness_host": [vp, sz, ctypes.POINTER(LoudnessClip), i, i, ctypes.c_float, vp, vp, vp, sz],
+        "gsv_level_init": [vp, sz, i] + [ctypes.c_double] * 5 + [ctypes.c_float, i, vp],
+        "gsv_level_push": [vp, vp, i, vp, i, vp, vp, vp],
+        "gsv_level_init_host": [vp, sz, i] + [ctypes.c_double] * 5 + [ctypes.c_float, i],
+        "gsv_level_push_host": [vp, vp, i, vp, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -311,6 +325,8 @@ def lib():
     L.gsv_track_out_capacity.restype = sz
     L.gsv_loudness_work_bytes.argtypes = [ctypes.POINTER(LoudnessClip), i, i]
     L.gsv_loudness_work_bytes.restype = sz
+    L.gsv_level_state_bytes.argtypes = [i, i]
+    L.gsv_level_state_bytes.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]
     L.gsv_align_workspace.restype = sz
     L.gsv_sola_workspace.argtypes = [i]

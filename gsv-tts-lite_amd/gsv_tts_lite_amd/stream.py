@@ -10,7 +10,8 @@ compute on this path and no CPU fallback.
 `gsv_stream_emit` also trims the head of a segment's first chunk and appends the mute behind its last, decides the chunk's length on
 the device, and the samples reach the host by one asynchronous copy behind a handle.  With a `track` (track.TrackResampler) the s16
 packets of a real-time track are made behind it by `gsv_track_push`, which reads the chunk's length from the emit record on the
-device, and travel in the same copy."""
+device, and travel in the same copy.  With a `level` (level.StreamLeveller) the emitted samples are levelled in place by
+`gsv_level_push` between the two, the same way: a track then carries levelled audio."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -58,9 +59,11 @@ class ChunkSplicer:
 class _Emitted:
     """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
 
-    def __init__(self, emitter, bufs, event, pcm_at=None):
+    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
         self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
+        self._level_at = level_at   # with a leveller: where its record starts
+        self.level = None           # and the record itself (level.LevelRecord), once result() has been called
 
     def ready(self) -> bool:
         return self._value is not None or self._event.query()
@@ -73,6 +76,9 @@ class _Emitted:
             host = self._bufs[1]
             n_out, k, h, _ = host[:4].view(torch.int32).tolist()
             self._value = (host[4: 4 + n_out].numpy().copy(), k, h)
+            if self._level_at is not None:
+                from . import level
+                self.level = level.record(host[self._level_at: self._level_at + level.RECORD_BYTES // 4].numpy().view("uint8"))
             if self._pcm_at is not None:
                 fmt = self._emitter.track.fmt
                 packets = int(host[self._pcm_at: self._pcm_at + 4].view(torch.int32)[0])
@@ -93,10 +99,15 @@ class ChunkEmitter:
     track: a track.TrackResampler on the chunks' device, or None.  With one, push() also enqueues `gsv_track_push` over the samples
     `gsv_stream_emit` wrote, their number read from its record on the device, and the packets with their record ride behind the
     samples in the same buffer and the same copy; `flush` ends the track's stream (the last chunk of a text).  The track's state
-    outlives `new_segment()`: one stream spans a text's segments and the mutes between them."""
+    outlives `new_segment()`: one stream spans a text's segments and the mutes between them.
 
-    def __init__(self, overlap_samples: int, search_len: int = 320, track=None):
-        self.overlap, self.search_len, self.track = int(overlap_samples), int(search_len), track
+    level: a level.StreamLeveller on the chunks' device, or None.  With one, push() enqueues `gsv_level_push` directly behind
+    `gsv_stream_emit`, in place on the samples it wrote, their number read from its record on the device; the samples handed out
+    -- and the track's packets -- are the levelled ones, and the handle carries the push's record in `level`.  Its state spans the
+    text like the track's, and `flush` ends its stream too."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None):
+        self.overlap, self.search_len, self.track, self.level = int(overlap_samples), int(search_len), track, level
         self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
         self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
 
@@ -123,18 +134,23 @@ class ChunkEmitter:
         nxt = 0 if self._cur is None else self._cur ^ 1
         used = 4 + n + int(mute_samples)
         pcm_cap = 0 if self.track is None else (self.track.capacity(used - 4) + 1) // 2      # int16 pairs as fp32 elements
-        dbuf, hbuf = bufs = self._buffers(used + (0 if self.track is None else 4 + pcm_cap), dev)
+        lrec = 0 if self.level is None else (used & 1) + 10       # the level record, 8-byte aligned, as fp32 elements
+        dbuf, hbuf = bufs = self._buffers(used + lrec + (0 if self.track is None else 4 + pcm_cap), dev)
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
                                   int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
                                   self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        pcm_at = None
+        pcm_at, level_at, n_samples = None, None, used - 4
+        if self.level is not None:       # [rec 4 | samples | level rec 10 (8-byte aligned) | ...]: in place, before the track reads them
+            level_at = used + (used & 1)
+            self.level.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
+            used += lrec
         if self.track is not None:       # [rec 4 | samples | track rec 4 | packets], all in fp32 elements
             pcm_at = used
-            self.track.enqueue(dbuf[4:].data_ptr(), used - 4, dbuf.data_ptr(), flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
+            self.track.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
             used += 4 + pcm_cap
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev, pcm_at)
+        return _Emitted(self, bufs, ev, pcm_at, level_at)

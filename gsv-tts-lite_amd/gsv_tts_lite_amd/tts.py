@@ -159,10 +159,27 @@ def _with_loudness(clip, rec):
     return clip
 
 
+def _with_level(clip, rec):
+    """a clip of a levelled stream: the running measure of the UNLEVELLED stream at its end, the gain of its last sample, and
+    whether any sample of the stream so far was set to the peak limit"""
+    clip.lufs, clip.gain, clip.limited = rec.lufs, rec.gain_last, rec.limited
+    return clip
+
+
 def _check_loudness(v):
     if v is not None and not np.isfinite(float(v)):
         raise ValueError("loudness target %r" % (v,))
     return None if v is None else float(v)
+
+
+def _check_loudness_seed(v):
+    """a stream's loudness_seed: None, or the last `lufs` of the same voice -- which is -inf when nothing was measured, and then
+    there is no seed either"""
+    if v is None or float(v) == -np.inf:
+        return None
+    if not np.isfinite(float(v)):
+        raise ValueError("loudness seed %r" % (v,))
+    return float(v)
 
 
 def cut_text(text: str, minlen: int = 10) -> list:
@@ -213,13 +230,13 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        self.emitter = ChunkEmitter(overlap_samples, track=track)        # track: the text's own TrackResampler, or None
+        self.emitter = ChunkEmitter(overlap_samples, track=track, level=level)       # the text's own TrackResampler / StreamLeveller, or None
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
         self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
@@ -963,7 +980,7 @@ class TTS:
                                          "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0, "、": 0.8, "・": 0.8},
                      stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                      temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                     sovits_model=None, debug=True, track=None):
+                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None):
         """TTS.py:289-504: generator of AudioClip chunks.  Per text segment the GPT streams cumulative token
         chunks (t2s.infer_stream); every chunk is decoded from the start of the segment with
         decode(stream_mode=True) -- only frames past `valid_start_idx` reach the flow / Generator -- and joined
@@ -972,7 +989,16 @@ class TTS:
         track: a track.TrackFormat, or None.  With one, every clip also carries `pcm` -- int16 [k, packet * channels], the whole
         packets of a real-time track at `pcm_rate` that its samples completed (k may be 0) --: one resampler state spans the
         text, its segments and the mutes between them, and the text's final clip flushes it.  The concatenated `pcm` is
-        AudioClip.to_pcm16 of the concatenated audio_data, bit for bit.  Nothing else about the clips changes."""
+        AudioClip.to_pcm16 of the concatenated audio_data, bit for bit.  Nothing else about the clips changes.
+
+        loudness: None, or a target in LUFS: the text's audio -- its segments and the mutes between them, one stream -- goes through
+        a running BS.1770 gain on the device (level.StreamLeveller) before it is handed out and before the track's
+        resampler: the concatenated audio_data is level.level() of the concatenated unlevelled clips, bit for bit.  Each clip then
+        carries lufs (the running loudness of the UNLEVELLED stream at its end), gain (of its last sample) and limited (a sample of
+        the stream so far was set to the peak limit).  loudness_seed: the last `lufs` of the same voice, to start at the right gain
+        instead of converging to it (None, or the -inf of a clip without a measurement: no seed); nothing is remembered between
+        calls."""
+        loudness, loudness_seed = _check_loudness(loudness), _check_loudness_seed(loudness_seed)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -999,6 +1025,7 @@ class TTS:
                 audio_len_s, cur_text_l, last_end_s = 0.0, 0, 0
                 cuts = cut_text(text, cut_minlen)
                 resampler = None if track is None else TrackResampler(track, self.samplerate, dev)
+                leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev)
                 for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
@@ -1045,10 +1072,14 @@ class TTS:
                                 last_subtitles_end = len(subtitles) - 1
                                 if not is_final and new_subtitles:
                                     new_subtitles[-1]["end_s"] = None
+                            if leveller is not None:
+                                audio = leveller.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             pcm = None if resampler is None else resampler.push(audio, flush=is_final and i == len(cuts) - 1)
                             audio = audio.float().cpu().numpy()
                         audio_len_s += len(audio) / self.samplerate
                         clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
+                        if leveller is not None:
+                            _with_level(clip, leveller.rec)
                         if resampler is not None:
                             clip.pcm, clip.pcm_rate = pcm, track.rate
                         yield clip
@@ -1062,6 +1093,10 @@ class TTS:
                     pass
                 self._empty_cache()
 
+    def _leveller(self, target, seed, dev):
+        from .level import StreamLeveller
+        return StreamLeveller(target, self.samplerate, dev, seed=seed)
+
     def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
                              is_cut_text=True, cut_minlen=10, cut_mute=0.4,
                              cut_mute_scale_map={"…": 2.0, ".": 1.5, "。": 1.5, "?": 1.5, "？": 1.5, "!": 1.5, "！": 1.5,
@@ -1069,7 +1104,7 @@ class TTS:
                                                  "、": 0.8, "・": 0.8},
                              stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                              temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                             sovits_model=None, debug=True, slots=None, seed=None, track=None):
+                             sovits_model=None, debug=True, slots=None, seed=None, track=None, loudness=None, loudness_seed=None):
         """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
         `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
         requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
@@ -1088,7 +1123,12 @@ class TTS:
         prompt are broadcast as in `infer_batched`.  Not available under a multi-rank engine.
 
         track: as in `infer_stream`; every text has its own resampler state, and its push is enqueued behind the chunk's epilogue
-        with the chunk's length read on the device, so the loop still waits for nothing."""
+        with the chunk's length read on the device, so the loop still waits for nothing.
+
+        loudness / loudness_seed: as in `infer_stream`, one value or one per text, None allowed per text (a wrong length raises
+        ValueError).  Every text with a value has its own leveller, enqueued between the chunk's epilogue and the track's push, in
+        place with the chunk's length read on the device: the loop still waits for nothing, a text's audio does not depend on its
+        neighbours, and a text without a value gets the clips it gets today."""
         with self._infer_lock:
             vq, gen = None, None
             try:
@@ -1097,6 +1137,8 @@ class TTS:
                 n = len(texts)
                 if n == 0:
                     return
+                loudness = [_check_loudness(v) for v in slot_sampling.per_request("loudness", loudness, n)]
+                loudness_seed = [_check_loudness_seed(v) for v in slot_sampling.per_request("loudness_seed", loudness_seed, n)]
                 speed = slot_sampling.per_request("speed", speed, n)
                 noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
                 if not all(s > 0 for s in speed):
@@ -1129,7 +1171,8 @@ class TTS:
                     gen_t = None if seeds[t] is None else torch.Generator().manual_seed(int(seeds[t]))
                     lines.append(_TextLine(text, cut_text(text, cut_minlen), self._ge_for(spk_audio_paths[t], sovits_model),
                                            overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t,
-                                           None if track is None else TrackResampler(track, self.samplerate, dev)))
+                                           None if track is None else TrackResampler(track, self.samplerate, dev),
+                                           None if loudness[t] is None else self._leveller(loudness[t], loudness_seed[t], dev)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1248,6 +1291,8 @@ class TTS:
             ln.seg, ln.y_overlap, ln.valid_start_idx, ln.chunk_idx, ln.last_subtitles_end = ln.seg + 1, None, 0, 0, 0
             ln.final_issued = False
         clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
+        if handle.level is not None:
+            _with_level(clip, handle.level)
         if pcm:
             clip.pcm, clip.pcm_rate = pcm[0], ln.emitter.track.fmt.rate
         return clip

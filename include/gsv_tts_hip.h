@@ -497,6 +497,56 @@ int gsv_loudness(const float* x, size_t n_x, const gsv_loudness_clip* clips, int
 int gsv_loudness_host(const float* x, size_t n_x, const gsv_loudness_clip* clips, int n_clips, int rate, float peak_limit,
                       float* out, gsv_loudness_record* records, void* work, size_t work_bytes);
 
+/* Stream leveller: a running BS.1770 gain for a stream of fp32 samples, whatever the chunks it arrives in (csrc/level.h,
+ * DESIGN 4.21).  Sample indices count from the start of the stream; knot h is l_h = (int)(0.4 * (h * 0.25) * rate), hop h is
+ * [l_h, l_(h+1)), block j is hops j .. j + 3.  The K-filter of gsv_loudness runs over the stream from zero state, complete hops
+ * only; S_h is a hop's sum of y^2, z_j = (S_j + S_(j+1) + S_(j+2) + S_(j+3)) / (0.4 rate); after hops < h both gates of
+ * gsv_loudness over blocks 0 .. h - 4 give kept_h and zbar_h, and P_h is the largest |x| of those hops.  The gain at knot h + 1:
+ *   z_eff = (w seed_z + kept_h zbar_h) / (w + kept_h), seed_z = 10^((seed_lufs + 0.691) / 10), w = seed_blocks (no seed: w = 0);
+ *   d = sqrt(10^((target + 0.691) / 10) / z_eff) (1 when w + kept_h is 0), clamped to [1 / G, G], G = 10^(max_gain_db / 20),
+ *   then to at most peak_limit / P_h;  A_(h+1) = min(max(d, A_h / r), A_h r), r = 10^(slew_db_s * 0.1 / 20);
+ *   A_0 = the seed's gain clamped to [1 / G, G], or 1.
+ * A sample n of hop h gets a = (float)fma(A_(h+1) - A_h, (double)(n - l_h) / (double)(l_(h+1) - l_h), A_h); y = x * a is one
+ * fp32 product; |y| > peak_limit becomes +-peak_limit and is counted.  Every decision is fp64; the knot a sample needs is
+ * decided from hops that ended before the sample's hop began, so the leveller adds no delay.
+ * A hop holding a NaN or an infinity is not measured and freezes the measure (GSV_LEVEL_NONFINITE): the last knot's gain holds.
+ * So does a full block history (GSV_LEVEL_FULL): max_seconds (1..3600) sizes it, (max_seconds - 0.4) / 0.1 + 1 blocks.
+ *   state: caller-owned, gsv_level_state_bytes(rate, max_seconds) bytes (0: a rate outside 4000..192000 or a bad max_seconds),
+ *   16-byte aligned, made by gsv_level_init: a header with every constant, the knots, the hop sums, the blocks, and a ring of
+ *   the newest samples in which an incomplete hop waits.  After N samples of the first stream
+ *   on a state as gsv_level_init left it, it is the same byte for byte however they were pushed (a flush marks the state ended
+ *   and leaves the old stream's arrays where the next has not overwritten them: unread, but there).
+ *   seed_lufs: NaN for no seed.  peak_limit > 0 (inf: no limit).
+ *   gsv_level_push: chunk fp32 [n_cap] (may be NULL when n_cap is 0); n_dev NULL or a device int32 holding the real length
+ *   (clamped to 0..n_cap) -- gsv_stream_emit's rec, so the call sits directly behind it --; out fp32 [n_cap], may be chunk;
+ *   flush ends the stream: the incomplete hop has been output and is never measured, and the next push starts a fresh stream
+ *   with the same constants.  rec (device, 8-byte aligned): the running measure of the UNLEVELLED stream after this push, the
+ *   gain of the push's first and last sample (an empty push: of the next sample), the samples clamped so far, the blocks,
+ *   those at or above the absolute gate, those past both gates, and flags.  A state gsv_level_init did not make is not read
+ *   through: the record says flags -1 and `out` is not written.  Two launches, nothing allocated, nothing read by the host.
+ *   gsv_level_init_host / gsv_level_push_host: the same over HOST memory from the same scalar routines -- the CPU path and
+ *   the device's oracle (device samples, records and state bytes equal the host's); they need no GPU.
+ * GSV_ERR_ARG: a null pointer, a negative size, a bad rate / max_seconds / constant, a state that is too small or misaligned,
+ * a misaligned record. */
+typedef struct {
+    double zbar;
+    float gain_first, gain_last;
+    int64_t clamped;
+    int32_t blocks, above_abs, kept, flags;
+} gsv_level_record;
+#define GSV_LEVEL_MEASURED 2
+#define GSV_LEVEL_NONFINITE 4   /* a NaN or an infinity in a hop: the measure is frozen */
+#define GSV_LEVEL_FULL 8        /* the block history is full: the measure is frozen */
+size_t gsv_level_state_bytes(int rate, int max_seconds);
+int gsv_level_init(void* state, size_t bytes, int rate, double target, double seed_lufs, double seed_blocks, double slew_db_s,
+                   double max_gain_db, float peak_limit, int max_seconds, void* stream);
+int gsv_level_push(void* state, const float* chunk, int n_cap, const int32_t* n_dev, int flush, float* out, gsv_level_record* rec,
+                   void* stream);
+int gsv_level_init_host(void* state, size_t bytes, int rate, double target, double seed_lufs, double seed_blocks,
+                        double slew_db_s, double max_gain_db, float peak_limit, int max_seconds);
+int gsv_level_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
+                        gsv_level_record* rec);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
