@@ -66,7 +66,7 @@ def _kv_close(got, want):
 
 @pytest.mark.parametrize("n_layer", [3, 24])
 def test_bf16_prefill_and_decode_hidden_vs_bf16_oracle(dev, n_layer):
-    """bench prompt shape: prompt pass (rowgemm / MFMA attention) and three per-sequence decode steps.  3 layers: the
+    """bench prompt shape: prompt pass (the bgemm chain of csrc/t2s_batch.h / MFMA attention) and three per-sequence decode steps.  3 layers: the
     tight bound.  24 layers: one-ulp operand flips (module docstring) are amplified by every following LayerNorm, so the
     bound is what 24 layers of that amplification measure, still 10x below the bf16-vs-fp32 distance (5e-2)."""
     from oracle import oracle as orc
