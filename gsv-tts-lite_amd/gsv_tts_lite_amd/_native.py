@@ -39,6 +39,7 @@ EXPORTS = [
     "gsv_track_state_bytes", "gsv_track_out_capacity", "gsv_track_init", "gsv_track_push", "gsv_track_init_host", "gsv_track_push_host",
     "gsv_loudness_work_bytes", "gsv_loudness", "gsv_loudness_host",
     "gsv_level_state_bytes", "gsv_level_init", "gsv_level_push", "gsv_level_init_host", "gsv_level_push_host",
+    "gsv_limiter_work_bytes", "gsv_limiter", "gsv_limiter_host",
 ]
 
 
@@ -157,6 +158,21 @@ class LevelRecord(ctypes.Structure):
 
 
 LEVEL_MEASURED, LEVEL_NONFINITE, LEVEL_FULL = 2, 4, 8       # GSV_LEVEL_*
+
+class LimiterClip(ctypes.Structure):
+    """gsv_limiter_clip: one clip of gsv_limiter; ceiling_db NaN: measure only"""
+    _fields_ = [("offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("ceiling_db", ctypes.c_float)]
+
+
+class LimiterRecord(ctypes.Structure):
+    """gsv_limiter_record: what gsv_limiter found and did per clip"""
+    _fields_ = [("true_peak_in", ctypes.c_float), ("true_peak_out", ctypes.c_float), ("min_gain", ctypes.c_float),
+                ("trim", ctypes.c_float), ("flags", ctypes.c_int32), ("lookahead", ctypes.c_int32), ("release", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+LIM_LIMITED, LIM_NONFINITE = 1, 4       # GSV_LIM_*
+LIM_TILE, LIM_MAX_LOOKAHEAD, LIM_MAX_RELEASE = 1024, 4096, 1 << 24      # csrc/limiter.h: LIM_TILE, LIM_MAX_L, LIM_MAX_R
 
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
@@ -283,6 +299,8 @@ def lib():
         "gsv_level_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_level_init_host": [vp, sz, i] + [ctypes.c_double] * 5 + [ctypes.c_float, i],
         "gsv_level_push_host": [vp, vp, i, vp, i, vp, vp],
+        "gsv_limiter": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz, vp],
+        "gsv_limiter_host": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -325,6 +343,8 @@ def lib():
     L.gsv_track_out_capacity.restype = sz
     L.gsv_loudness_work_bytes.argtypes = [ctypes.POINTER(LoudnessClip), i, i]
     L.gsv_loudness_work_bytes.restype = sz
+    L.gsv_limiter_work_bytes.argtypes = [ctypes.POINTER(LimiterClip), i]
+    L.gsv_limiter_work_bytes.restype = sz
     L.gsv_level_state_bytes.argtypes = [i, i]
     L.gsv_level_state_bytes.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]

@@ -44,6 +44,7 @@ gsv_align_viterbi, replacing TTS.py:1744-1797) and the word-timing / text-span b
 from __future__ import annotations
 
 import logging
+import math
 import numbers
 import os
 import re
@@ -98,6 +99,8 @@ class AudioClip:
         self.lufs = None            # a clip made with loudness= (or by normalised()): the integrated loudness before the gain,
         self.gain = None            # the gain applied (np.float32: audio_data is the unnormalised samples times it)
         self.limited = None         # and whether the peak limit, not the target, set that gain
+        self.dbtp = None            # a clip made with true_peak= (or by limited_to()): its true peak in dBTP behind the limiter;
+                                    # `limited` then says whether the limiter had to act
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -146,6 +149,21 @@ class AudioClip:
         audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
         return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text), rec)
 
+    def true_peak(self) -> float:
+        """the true peak of audio_data in dBTP (limiter.true_peak: the largest magnitude of the clip oversampled 4x, measured on
+        the GPU when there is one, by the same arithmetic on the CPU otherwise); -inf for silence"""
+        from . import limiter
+        return limiter.true_peak(self.audio_data, self.samplerate)
+
+    def limited_to(self, ceiling_db: float = -1.0) -> "AudioClip":
+        """a new clip held at or under `ceiling_db` dBTP by the look-ahead limiter (limiter.limit), same subtitles and text; its
+        dbtp / limited say what came out and whether the limiter acted, lufs / gain are kept"""
+        from . import limiter
+        audio, rec = limiter.limit(self.audio_data, self.samplerate, ceiling_db)
+        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
+        out.lufs, out.gain = self.lufs, self.gain
+        return _with_true_peak(out, rec)
+
     def _save_wav(self, save_path):
         import wave
         pcm = (np.clip(self.audio_data, -1.0, 1.0) * 32767.0).astype("<i2")
@@ -157,6 +175,23 @@ class AudioClip:
 def _with_loudness(clip, rec):
     clip.lufs, clip.gain, clip.limited = rec.lufs, rec.gain, rec.limited
     return clip
+
+
+def _with_records(clip, rec, lim):
+    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim) or both"""
+    if rec is not None:
+        _with_loudness(clip, rec)
+    return clip if lim is None else _with_true_peak(clip, lim)
+
+
+def _with_true_peak(clip, rec):
+    clip.dbtp, clip.limited = rec.dbtp_out, rec.limited
+    return clip
+
+
+def _check_true_peak(v):
+    from . import limiter
+    return limiter.check_ceiling(v)
 
 
 def _with_level(clip, rec):
@@ -823,11 +858,16 @@ class TTS:
     @torch.inference_mode()
     def infer(self, spk_audio_path, prompt_audio_path, prompt_audio_text, text, return_subtitles=False, top_k=15,
               top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-              sovits_model=None, loudness=None):
+              sovits_model=None, loudness=None, true_peak=None):
         """loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
         peak rule, trailing 0.2 s of zeros included -- is measured and scaled to it on the device before the download
-        (loudness.py); the clip then carries lufs (before the gain), gain and limited."""
-        loudness = _check_loudness(loudness)
+        (loudness.py); the clip then carries lufs (before the gain), gain and limited.
+
+        true_peak: None, or a ceiling in dBTP <= 0 (-1.0 is EBU R128's): the clip that would have been returned is held under it
+        by the look-ahead limiter on the device (limiter.py) and carries dbtp (its true peak behind the limiter) and
+        limited (the limiter acted).  With loudness= as well the gain to the target is applied whatever the peak becomes, and the
+        limiter then holds the ceiling: the loudness that comes out is what the limiter leaves."""
+        loudness, true_peak = _check_loudness(loudness), _check_true_peak(true_peak)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -863,9 +903,10 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
-                if loudness is not None:
-                    audio, rec = self._finish_on_device(audio.float(), loudness)
-                    return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text), rec)
+                if loudness is not None or true_peak is not None:
+                    audio, rec, lim = self._finish_on_device(audio.float(), loudness, true_peak)
+                    return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text),
+                                         rec, lim)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -875,28 +916,40 @@ class TTS:
             finally:
                 self._empty_cache()
 
-    def _finish_on_device(self, audio, target):
-        """the tail of infer / infer_vc with loudness=: the peak rule (an IEEE division by max(peak, 1): dividing by 1 is exact, so
-        the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_loudness call
-        over the finished clip with its record written behind the samples: ONE download carries both -> (numpy samples, record)"""
+    def _finish_on_device(self, audio, target, ceiling=None):
+        """the tail of infer / infer_vc with loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1): dividing by 1 is
+        exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_loudness
+        call (target) and one gsv_limiter call (ceiling) over the finished clip in place, their records written behind the samples:
+        ONE download carries all -> (numpy samples, loudness record or None, limiter record or None).  Ahead of the limiter the
+        gain to the target is applied with no peak limit: the limiter holds the ceiling."""
+        from . import limiter as lm
         from . import loudness as ld
         if audio.numel():
             audio = audio / audio.abs().max().clamp(min=1)
         n = audio.numel() + int(0.2 * self.samplerate)
-        tail = (n + 1) // 2 * 2 - audio.numel() + ld.RECORD_BYTES // 4         # zeros to n, to an 8-byte boundary, the record
+        words = (ld.RECORD_BYTES // 4 if target is not None else 0) + (lm.RECORD_BYTES // 4 if ceiling is not None else 0)
+        tail = (n + 1) // 2 * 2 - audio.numel() + words                        # zeros to n, to an 8-byte boundary, the records
         buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
-        rec = buf[buf.numel() - ld.RECORD_BYTES // 4:].view(torch.uint8)
-        ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0, buf[:n], rec)
+        at = buf.numel() - words
+        if target is not None:
+            ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0 if ceiling is None else math.inf, buf[:n],
+                          buf[at: at + ld.RECORD_BYTES // 4].view(torch.uint8))
+        if ceiling is not None:
+            L, R = lm.times(self.samplerate)
+            lm.run_packed(buf[:n], [0], [n], [ceiling], L, R, buf[:n], buf[buf.numel() - lm.RECORD_BYTES // 4:].view(torch.uint8))
         host = buf.cpu().numpy()
-        return host[:n], ld.records(host[host.size - ld.RECORD_BYTES // 4:].view(np.uint8))[0]
+        rec = ld.records(host[at: at + ld.RECORD_BYTES // 4].view(np.uint8))[0] if target is not None else None
+        lim = lm.records(host[host.size - lm.RECORD_BYTES // 4:].view(np.uint8))[0] if ceiling is not None else None
+        return host[:n], rec, lim
 
     @torch.inference_mode()
     def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
-                 loudness=None):
+                 loudness=None, true_peak=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
         decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
-        loudness: as in infer."""
-        loudness = _check_loudness(loudness)
+        loudness, true_peak: as in infer."""
+        loudness, true_peak = _check_loudness(loudness), _check_true_peak(true_peak)
+        finish = loudness is not None or true_peak is not None
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -913,16 +966,16 @@ class TTS:
                 phones, word2ph, _, norm_text = self._phones_and_bert(prompt_audio_text)
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
-                if loudness is not None:
-                    audio, rec = self._finish_on_device(audio[0, 0, :].float(), loudness)
+                if finish:
+                    audio, rec, lim = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak)
                 else:
                     audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
                 self._close_subtitles(subtitles, word2ph, 0.2)
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
-                if loudness is not None:
-                    return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
-                                                    prompt_audio_text), rec)
+                if finish:
+                    return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
+                                                   prompt_audio_text), rec, lim)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1329,7 +1382,7 @@ class TTS:
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
-                      initial_suppression_steps=0, loudness=None):
+                      initial_suppression_steps=0, loudness=None, true_peak=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
 
@@ -1349,7 +1402,12 @@ class TTS:
         loudness: None, a target in LUFS for every text, or one value or None per TEXT (a wrong length raises ValueError).  The
         finished clips -- mutes between segments included -- of the texts with a value are measured and scaled in ONE packed
         gsv_loudness call (loudness.py), on the gathering rank under a multi-rank engine; those clips carry lufs,
-        gain and limited.  A text with None comes back exactly as without the parameter."""
+        gain and limited.  A text with None comes back exactly as without the parameter.
+
+        true_peak: None, a ceiling in dBTP <= 0 for every text, or one value or None per TEXT (a wrong length raises ValueError).
+        The finished clips of the texts with a value -- behind the gain to their loudness target, which is then applied whatever
+        the peak becomes -- are held under it in ONE packed gsv_limiter call (limiter.py) and carry dbtp and
+        limited, as in infer."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
@@ -1359,6 +1417,10 @@ class TTS:
                                                              if slot_sampling.is_sequence(loudness) else [loudness] * len(texts))]
                     if all(v is None for v in loudness):
                         loudness = None
+                if true_peak is not None:
+                    true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, len(texts))]
+                    if all(v is None for v in true_peak):
+                        true_peak = None
                 segmented = slot_sampling.is_sequence(speed) or slot_sampling.is_sequence(noise_scale)
                 if segmented:   # one value per text: the lengths are checked before any device work
                     speed = slot_sampling.per_request("speed", speed, len(texts))
@@ -1544,11 +1606,23 @@ class TTS:
                     clips.append(AudioClip(self.audio_queue, a, self.samplerate, len(a) / self.samplerate, subtitles, t))
                 if loudness is not None:    # one packed call over the texts that asked
                     from . import loudness as ld
-                    pick = [i for i, v in enumerate(loudness) if v is not None]
-                    scaled, recs = ld.normalise([clips[i].audio_data for i in pick], self.samplerate, [loudness[i] for i in pick], 1.0, device=dev)
-                    for i, a, rec in zip(pick, scaled, recs):
+                    held = [true_peak is not None and true_peak[i] is not None for i in range(len(clips))]
+                    for limit, hold in ((1.0, False), (math.inf, True)):        # ahead of the limiter no peak limit binds
+                        pick = [i for i, v in enumerate(loudness) if v is not None and held[i] == hold]
+                        if not pick:
+                            continue
+                        scaled, recs = ld.normalise([clips[i].audio_data for i in pick], self.samplerate, [loudness[i] for i in pick], limit,
+                                                    device=dev)
+                        for i, a, rec in zip(pick, scaled, recs):
+                            clips[i].audio_data = a
+                            _with_loudness(clips[i], rec)
+                if true_peak is not None:   # one packed call over the texts that asked
+                    from . import limiter as lm
+                    pick = [i for i, v in enumerate(true_peak) if v is not None]
+                    under, recs = lm.limit([clips[i].audio_data for i in pick], self.samplerate, [true_peak[i] for i in pick], device=dev)
+                    for i, a, rec in zip(pick, under, recs):
                         clips[i].audio_data = a
-                        _with_loudness(clips[i], rec)
+                        _with_true_peak(clips[i], rec)
                 return tuple(clips)
             finally:
                 self._empty_cache()

@@ -547,6 +547,43 @@ int gsv_level_init_host(void* state, size_t bytes, int rate, double target, doub
 int gsv_level_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
                         gsv_level_record* rec);
 
+/* True-peak limiter: the true peak of n_clips clips of one packed fp32 buffer, and each clip held under its ceiling by a
+ * look-ahead limiter (csrc/limiter.h).  With T = 10^(ceiling_db / 20), L = lookahead and s = 1 / release:
+ *   e[n] = max |u[4n-3 .. 4n+3]|, u the clip oversampled 4x by the 49-tap sinc(k/4) kaiser(49, 8) (12 taps per phase, phase 0
+ *   the identity, zeros outside the clip); c = min(1, T / e); h[n] = min c[n .. n+L-1] (c = 1 behind the end);
+ *   r[n] = min(h[n], min_{k<=n}(h[k] + (n-k) s)); g[n] = min(c[n], (sum_{i<L} r[n-i]) (1/L)) with r[m<0] = r[0]; y1 = g x;
+ *   t = min(1, T / truepeak(y1)); y = t y1.  All fp32.
+ *   x: fp32 [n_x]; clip c is x[offset, offset + n_samples), mono; the clips do not overlap.  ceiling_db: dBTP in -200..0, NaN
+ *   for a clip that is only measured.  lookahead 1..4096 and release 1..2^24 are in samples.
+ *   out: NULL (measure only), x (in place) or a second buffer of n_x floats; only [offset, offset + n_samples) of each clip
+ *   is written.  A clip whose true peak is at or under its ceiling is copied (in place: nothing is written).
+ *   records [n_clips]: true_peak_in = max e; true_peak_out = trim * truepeak(y1) (true_peak_in for a clip that was not
+ *   limited); min_gain = min g and trim = t (both 1 for such a clip); flags; the look-ahead and the release of the call.  A
+ *   clip holding a NaN or an infinity (GSV_LIM_NONFINITE) comes back unchanged, its peaks that NaN or infinity.
+ *   work: caller-owned, gsv_limiter_work_bytes(clips, n_clips) bytes (0: bad arguments), 16-byte aligned.
+ *   gsv_limiter: x, out, records and work are DEVICE memory, clips is HOST memory.  One small upload and at most six launches
+ *   on `stream`; nothing allocated, nothing read back by the host.
+ *   gsv_limiter_host: the same over HOST memory from the same scalar routines -- the CPU path and the device's oracle
+ *   (device records and samples equal the host's bit for bit); it needs no GPU.
+ * GSV_ERR_ARG: a null pointer, a bad look-ahead / release / ceiling / clip count (1..65535), a clip outside [0, n_x), a
+ * workspace that is too small or misaligned. */
+typedef struct {
+    int64_t offset;         /* first sample of the clip in x */
+    int32_t n_samples;
+    float ceiling_db;       /* dBTP; NaN: measure only */
+} gsv_limiter_clip;
+typedef struct {
+    float true_peak_in, true_peak_out, min_gain, trim;
+    int32_t flags, lookahead, release, reserved;
+} gsv_limiter_record;
+#define GSV_LIM_LIMITED 1       /* the true peak was above the ceiling: the clip was limited */
+#define GSV_LIM_NONFINITE 4     /* a NaN or an infinity among the samples */
+size_t gsv_limiter_work_bytes(const gsv_limiter_clip* clips, int n_clips);
+int gsv_limiter(const float* x, size_t n_x, const gsv_limiter_clip* clips, int n_clips, int lookahead, int release, float* out,
+                gsv_limiter_record* records, void* work, size_t work_bytes, void* stream);
+int gsv_limiter_host(const float* x, size_t n_x, const gsv_limiter_clip* clips, int n_clips, int lookahead, int release,
+                     float* out, gsv_limiter_record* records, void* work, size_t work_bytes);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
