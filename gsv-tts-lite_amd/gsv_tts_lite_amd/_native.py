@@ -40,6 +40,8 @@ EXPORTS = [
     "gsv_loudness_work_bytes", "gsv_loudness", "gsv_loudness_host",
     "gsv_level_state_bytes", "gsv_level_init", "gsv_level_push", "gsv_level_init_host", "gsv_level_push_host",
     "gsv_limiter_work_bytes", "gsv_limiter", "gsv_limiter_host",
+    "gsv_limstream_state_bytes", "gsv_limstream_out_capacity", "gsv_limstream_init", "gsv_limstream_push", "gsv_limstream_init_host",
+    "gsv_limstream_push_host",
 ]
 
 
@@ -172,6 +174,16 @@ class LimiterRecord(ctypes.Structure):
 
 
 LIM_LIMITED, LIM_NONFINITE = 1, 4       # GSV_LIM_*
+
+
+class LimstreamRecord(ctypes.Structure):
+    """gsv_limstream_record: what one gsv_limstream_push emitted and did"""
+    _fields_ = [("emitted", ctypes.c_int32), ("flags", ctypes.c_int16), ("lookahead", ctypes.c_int16), ("peak_in", ctypes.c_float),
+                ("peak_run", ctypes.c_float), ("min_gain", ctypes.c_float), ("release", ctypes.c_int32), ("total", ctypes.c_int64)]
+
+
+LIMS_LIMITED, LIMS_LIMITED_EVER, LIMS_NONFINITE = 1, 2, 4       # GSV_LIMS_*
+LIMS_MAX_CHUNK = 1 << 20                # csrc/limstream.h: samples of one push
 LIM_TILE, LIM_MAX_LOOKAHEAD, LIM_MAX_RELEASE = 1024, 4096, 1 << 24      # csrc/limiter.h: LIM_TILE, LIM_MAX_L, LIM_MAX_R
 
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
@@ -301,6 +313,10 @@ def lib():
         "gsv_level_push_host": [vp, vp, i, vp, i, vp, vp],
         "gsv_limiter": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz, vp],
         "gsv_limiter_host": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz],
+        "gsv_limstream_init": [vp, sz, ctypes.c_float, i, i, vp],
+        "gsv_limstream_push": [vp, vp, i, vp, i, vp, vp, vp],
+        "gsv_limstream_init_host": [vp, sz, ctypes.c_float, i, i],
+        "gsv_limstream_push_host": [vp, vp, i, vp, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -345,6 +361,10 @@ def lib():
     L.gsv_loudness_work_bytes.restype = sz
     L.gsv_limiter_work_bytes.argtypes = [ctypes.POINTER(LimiterClip), i]
     L.gsv_limiter_work_bytes.restype = sz
+    L.gsv_limstream_state_bytes.argtypes = [i, i]
+    L.gsv_limstream_state_bytes.restype = sz
+    L.gsv_limstream_out_capacity.argtypes = [i, i]
+    L.gsv_limstream_out_capacity.restype = sz
     L.gsv_level_state_bytes.argtypes = [i, i]
     L.gsv_level_state_bytes.restype = sz
     L.gsv_align_workspace.argtypes = [i, i]

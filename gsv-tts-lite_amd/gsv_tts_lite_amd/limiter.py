@@ -9,7 +9,16 @@ one call:
 
 On a GPU device a call is `gsv_limiter` (one small upload, at most six launches); on "cpu" the host twin `gsv_limiter_host` runs the
 same scalar routines and gives the same bits.  A clip already under its ceiling comes back bit for bit; so does one holding a NaN or
-an infinity, flagged `nonfinite`."""
+an infinity, flagged `nonfinite`.
+
+Streams (csrc/limstream.h): the same stages 1 - 6 without the trim, as a state that emits every sample once the
+look-ahead behind it has arrived, independent of how the stream was cut into pushes:
+
+    lm = StreamLimiter(-1.0, 32000, device="cuda:0")
+    for chunk, last in chunks:
+        out = lm.push(chunk, flush=last)           # float32 numpy; lm.delay samples behind the input until the flush
+    lm.rec.limited_ever, lm.rec.dbtp_in, lm.rec.min_gain
+    y, rec = limit_stream(x, 32000, ceiling_db=-1.0)           # one push with flush"""
 from __future__ import annotations
 
 import ctypes
@@ -194,3 +203,132 @@ def limit(clips, rate: int, ceiling_db=-1.0, lookahead_ms: float = 1.5, release_
             host = out.cpu().numpy() if host is None else host
             res.append(host[o:o + n].reshape(np.shape(c)).copy())
     return (res[0], recs[0]) if single else (res, recs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# streams (csrc/limstream.h)
+# ----------------------------------------------------------------------------------------------------------------------
+_SREC = np.dtype([("emitted", "<i4"), ("flags", "<i2"), ("lookahead", "<i2"), ("peak_in", "<f4"), ("peak_run", "<f4"),
+                  ("min_gain", "<f4"), ("release", "<i4"), ("total", "<i8")])
+assert _SREC.itemsize == ctypes.sizeof(N.LimstreamRecord)
+STREAM_RECORD_BYTES = _SREC.itemsize
+
+
+class StreamLimiterRecord:
+    """emitted: samples the push handed out; total: samples the stream has handed out; peak_in: the largest finite true-peak
+    envelope among the push's samples as they came (np.float32, 0 for none), peak_run: among the stream's so far; min_gain: the
+    smallest gain among the push's samples (1 for none); limited: a gain below 1 in this push, limited_ever: in the stream so far;
+    nonfinite: a sample of this push whose envelope is a NaN or an infinity (copied); lookahead / release: samples"""
+
+    __slots__ = ("emitted", "total", "peak_in", "peak_run", "min_gain", "limited", "limited_ever", "nonfinite", "lookahead", "release")
+
+    def __init__(self, emitted, flags, lookahead, peak_in, peak_run, min_gain, release, total):
+        self.emitted, self.total = int(emitted), int(total)
+        self.peak_in, self.peak_run, self.min_gain = np.float32(peak_in), np.float32(peak_run), np.float32(min_gain)
+        self.limited = bool(flags & N.LIMS_LIMITED)
+        self.limited_ever = bool(flags & N.LIMS_LIMITED_EVER)
+        self.nonfinite = bool(flags & N.LIMS_NONFINITE)
+        self.lookahead, self.release = int(lookahead), int(release)
+
+    @property
+    def dbtp_in(self) -> float:
+        """the highest true peak of the unlimited stream so far, dBTP"""
+        return dbtp(self.peak_run)
+
+    def __repr__(self):
+        return "StreamLimiterRecord(emitted=%d, total=%d, peak_in=%r, peak_run=%r, min_gain=%r, limited=%r, limited_ever=%r, nonfinite=%r)" % (
+            self.emitted, self.total, float(self.peak_in), float(self.peak_run), float(self.min_gain), self.limited, self.limited_ever,
+            self.nonfinite)
+
+
+def stream_record(raw):
+    """the 32 record bytes (a tensor on any device, or a numpy array of them) -> StreamLimiterRecord"""
+    raw = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    return StreamLimiterRecord(*np.frombuffer(raw.tobytes()[:STREAM_RECORD_BYTES], dtype=_SREC)[0].tolist())
+
+
+class StreamLimiter:
+    """One stream held under `ceiling_db` dBTP: the clip limiter's stages 1 - 6 over the whole stream, without the
+    trim.  push(x, flush) -> float32 numpy: after N samples in all, max(0, N - delay) have come out, so a push may return nothing; a
+    flush returns the rest and the next push starts a fresh stream with the same constants.  The samples never depend on how the
+    stream was cut into pushes.  delay = lookahead + 5 samples.  On a GPU device a push is three launches of `gsv_limstream_push`;
+    on "cpu" the host twin runs the same scalar routines and gives the same bytes."""
+
+    def __init__(self, ceiling_db, rate: int, device="cpu", lookahead_ms: float = 1.5, release_ms: float = 50.0):
+        self.ceiling_db = check_ceiling(ceiling_db)
+        if self.ceiling_db is None:
+            raise ValueError("a stream limiter needs a ceiling")
+        self.rate, self.device = int(rate), torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lookahead, self.release = times(rate, lookahead_ms, release_ms)
+        self.delay = self.lookahead + 5
+        L = N.lib()
+        nbytes = L.gsv_limstream_state_bytes(self.lookahead, self.release)
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                N.check(L.gsv_limstream_init(self.state.data_ptr(), nbytes, self.ceiling_db, self.lookahead, self.release,
+                                             N.current_stream_ptr(self.device)))
+        else:
+            N.check(L.gsv_limstream_init_host(self.state.data_ptr(), nbytes, self.ceiling_db, self.lookahead, self.release))
+        self._rec = None        # the last push's record bytes, on the device of the call
+
+    @property
+    def on_device(self) -> bool:
+        return self.device.type == "cuda"
+
+    def capacity(self, n_cap: int) -> int:
+        """the floats `out` must hold for a push of at most n_cap samples"""
+        return int(n_cap) + self.delay
+
+    def enqueue(self, chunk_ptr: int, n_cap: int, n_dev_ptr, flush: bool, out_ptr: int, rec_ptr: int):
+        """the raw device call on the current stream: nothing is read back (ChunkEmitter's use)"""
+        N.check(N.lib().gsv_limstream_push(self.state.data_ptr(), chunk_ptr or None, int(n_cap), n_dev_ptr, int(bool(flush)),
+                                           out_ptr or None, rec_ptr, N.current_stream_ptr(self.device)))
+
+    def _push_once(self, x: torch.Tensor, flush: bool):
+        n = int(x.numel())
+        out = torch.empty(self.capacity(n), dtype=torch.float32, device=self.device)
+        rec = torch.empty(STREAM_RECORD_BYTES // 8, dtype=torch.int64, device=self.device)      # 8-byte aligned
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                self.enqueue(x.data_ptr(), n, None, flush, out.data_ptr(), rec.data_ptr())
+        else:
+            N.check(N.lib().gsv_limstream_push_host(self.state.data_ptr(), x.data_ptr() or None, n, None, int(bool(flush)),
+                                                    out.data_ptr(), rec.data_ptr()))
+        return out, rec
+
+    def push_tensor(self, x: torch.Tensor, flush: bool = False) -> torch.Tensor:
+        """x on the limiter's device -> the samples this push emits, a new fp32 tensor there.  Its length is read from the record, so
+        the call waits for the push.  Input longer than one push may be (2^20 samples) goes in as several, which changes no byte;
+        `rec` is then the last one's."""
+        x = x.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        parts = []
+        cuts = list(range(0, int(x.numel()), N.LIMS_MAX_CHUNK)) or [0]
+        for k, at in enumerate(cuts):
+            out, rec = self._push_once(x[at: at + N.LIMS_MAX_CHUNK], flush and k + 1 == len(cuts))
+            self._rec = stream_record(rec.view(torch.uint8))
+            parts.append(out[: self._rec.emitted])
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def push(self, x, flush: bool = False) -> np.ndarray:
+        return self.push_tensor(torch.as_tensor(x), flush).cpu().numpy()
+
+    @property
+    def rec(self):
+        """the last push's StreamLimiterRecord (None before the first push)"""
+        return self._rec
+
+
+def limit_stream(x, rate: int, ceiling_db=-1.0, lookahead_ms: float = 1.5, release_ms: float = 50.0, device=None):
+    """the whole signal limited as one stream: one push with flush -> (float32 numpy, StreamLimiterRecord).  device: where the
+    samples are, else the GPU when there is one, else the CPU -- the bytes are the same."""
+    if device is None:
+        if isinstance(x, torch.Tensor) and x.device.type == "cuda":
+            device = x.device
+        else:
+            device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+    lm = StreamLimiter(ceiling_db, rate, device, lookahead_ms, release_ms)
+    out = lm.push(x, flush=True)
+    return out, lm.rec

@@ -59,18 +59,21 @@ class ChunkSplicer:
 class _Emitted:
     """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
 
-    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None):
+    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
         self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
         self._level_at = level_at   # with a leveller: where its record starts
         self.level = None           # and the record itself (level.LevelRecord), once result() has been called
+        self._limit_at = limit_at   # with a limiter: where its record starts; its samples lie behind the record
+        self.limit = None           # and the record itself (limiter.StreamLimiterRecord), once result() has been called
 
     def ready(self) -> bool:
         return self._value is not None or self._event.query()
 
     def result(self):
         """-> (samples float32 numpy [rec[0]], SOLA offset, head offset); with a track also its packets, int16 numpy
-        [packets, packet * channels]"""
+        [packets, packet * channels].  With a limiter the samples are the ones it emitted with this push: as many as its record
+        says, which may be none."""
         if self._value is None:
             self._event.synchronize()
             host = self._bufs[1]
@@ -79,6 +82,11 @@ class _Emitted:
             if self._level_at is not None:
                 from . import level
                 self.level = level.record(host[self._level_at: self._level_at + level.RECORD_BYTES // 4].numpy().view("uint8"))
+            if self._limit_at is not None:
+                from . import limiter
+                at = self._limit_at
+                self.limit = limiter.stream_record(host[at: at + limiter.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
+                self._value = (host[at + 8: at + 8 + self.limit.emitted].numpy().copy(), k, h)
             if self._pcm_at is not None:
                 fmt = self._emitter.track.fmt
                 packets = int(host[self._pcm_at: self._pcm_at + 4].view(torch.int32)[0])
@@ -104,10 +112,16 @@ class ChunkEmitter:
     level: a level.StreamLeveller on the chunks' device, or None.  With one, push() enqueues `gsv_level_push` directly behind
     `gsv_stream_emit`, in place on the samples it wrote, their number read from its record on the device; the samples handed out
     -- and the track's packets -- are the levelled ones, and the handle carries the push's record in `level`.  Its state spans the
-    text like the track's, and `flush` ends its stream too."""
+    text like the track's, and `flush` ends its stream too.
 
-    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None):
-        self.overlap, self.search_len, self.track, self.level = int(overlap_samples), int(search_len), track, level
+    limit: a limiter.StreamLimiter on the chunks' device, or None.  With one, push() enqueues `gsv_limstream_push` behind the
+    leveller (emit -> level -> limit -> track), out of place into its own region of the buffer, the chunk's length read from
+    `gsv_stream_emit`'s record on the device; the samples handed out are the ones the limiter emitted with this push -- `delay`
+    samples behind the chunk, so the first chunk of a text is that much shorter and the flushing one that much longer --, the
+    track reads them with their number from the limiter's record, and the handle carries that record in `limit`."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None):
+        self.overlap, self.search_len, self.track, self.level, self.limit = int(overlap_samples), int(search_len), track, level, limit
         self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
         self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
 
@@ -133,24 +147,33 @@ class ChunkEmitter:
         prev = None if self._cur is None else self._tails[self._cur]
         nxt = 0 if self._cur is None else self._cur ^ 1
         used = 4 + n + int(mute_samples)
-        pcm_cap = 0 if self.track is None else (self.track.capacity(used - 4) + 1) // 2      # int16 pairs as fp32 elements
+        lim_cap = 0 if self.limit is None else self.limit.capacity(used - 4)     # the most samples the limiter emits
+        pcm_cap = 0 if self.track is None else (self.track.capacity(lim_cap or used - 4) + 1) // 2      # int16 pairs as fp32 elements
         lrec = 0 if self.level is None else (used & 1) + 10       # the level record, 8-byte aligned, as fp32 elements
-        dbuf, hbuf = bufs = self._buffers(used + lrec + (0 if self.track is None else 4 + pcm_cap), dev)
+        mrec = 0 if self.limit is None else ((used + lrec) & 1) + 8 + lim_cap      # the limiter's record, 8-byte aligned, and its samples
+        dbuf, hbuf = bufs = self._buffers(used + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
                                   int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
                                   self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        pcm_at, level_at, n_samples = None, None, used - 4
+        pcm_at, level_at, limit_at, n_samples = None, None, None, used - 4
+        src, src_cap, src_len = dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr()       # what the track reads: samples, capacity, length
         if self.level is not None:       # [rec 4 | samples | level rec 10 (8-byte aligned) | ...]: in place, before the track reads them
             level_at = used + (used & 1)
             self.level.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
             used += lrec
+        if self.limit is not None:       # [... | limiter rec 8 (8-byte aligned) | its samples n + delay | ...]: out of place
+            limit_at = used + (used & 1)
+            self.limit.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[limit_at + 8:].data_ptr(),
+                               dbuf[limit_at:].data_ptr())
+            src, src_cap, src_len = dbuf[limit_at + 8:].data_ptr(), lim_cap, dbuf[limit_at:].data_ptr()
+            used += mrec
         if self.track is not None:       # [rec 4 | samples | track rec 4 | packets], all in fp32 elements
             pcm_at = used
-            self.track.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
+            self.track.enqueue(src, src_cap, src_len, flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
             used += 4 + pcm_cap
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev, pcm_at, level_at)
+        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at)

@@ -101,6 +101,8 @@ class AudioClip:
         self.limited = None         # and whether the peak limit, not the target, set that gain
         self.dbtp = None            # a clip made with true_peak= (or by limited_to()): its true peak in dBTP behind the limiter;
                                     # `limited` then says whether the limiter had to act
+        self.dbtp_in = None         # a clip of a stream made with true_peak=: the highest true peak in dBTP of the UNLIMITED stream so
+        self.gain_min = None        # far, and the smallest gain among this clip's samples; `limited`: the limiter has acted so far
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -201,6 +203,14 @@ def _with_level(clip, rec):
     return clip
 
 
+def _with_stream_limit(clip, rec):
+    """a clip of a stream held under a ceiling (limiter.StreamLimiterRecord): whether the limiter has acted on the stream so far, the
+    highest true peak of the unlimited stream so far, the smallest gain among the clip's samples.  No `dbtp`: the output's true
+    peak is not measured"""
+    clip.limited, clip.dbtp_in, clip.gain_min = rec.limited_ever, rec.dbtp_in, rec.min_gain
+    return clip
+
+
 def _check_loudness(v):
     if v is not None and not np.isfinite(float(v)):
         raise ValueError("loudness target %r" % (v,))
@@ -265,13 +275,15 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        self.emitter = ChunkEmitter(overlap_samples, track=track, level=level)       # the text's own TrackResampler / StreamLeveller, or None
+        # the text's own TrackResampler / StreamLeveller / StreamLimiter, or None (without a limiter: the call as it always was)
+        self.emitter = (ChunkEmitter(overlap_samples, track=track, level=level) if limit is None else
+                        ChunkEmitter(overlap_samples, track=track, level=level, limit=limit))
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
         self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
@@ -1033,7 +1045,7 @@ class TTS:
                                          "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0, "、": 0.8, "・": 0.8},
                      stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                      temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None):
+                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None, true_peak=None):
         """TTS.py:289-504: generator of AudioClip chunks.  Per text segment the GPT streams cumulative token
         chunks (t2s.infer_stream); every chunk is decoded from the start of the segment with
         decode(stream_mode=True) -- only frames past `valid_start_idx` reach the flow / Generator -- and joined
@@ -1050,8 +1062,20 @@ class TTS:
         carries lufs (the running loudness of the UNLEVELLED stream at its end), gain (of its last sample) and limited (a sample of
         the stream so far was set to the peak limit).  loudness_seed: the last `lufs` of the same voice, to start at the right gain
         instead of converging to it (None, or the -inf of a clip without a measurement: no seed); nothing is remembered between
-        calls."""
-        loudness, loudness_seed = _check_loudness(loudness), _check_loudness_seed(loudness_seed)
+        calls.
+
+        true_peak: None, or a ceiling in dBTP <= 0: the text's audio -- one stream, as for loudness= -- goes through the stream
+        limiter on the device (limiter.StreamLimiter) behind the leveller and before the track's resampler: the
+        concatenated audio_data is limiter.limit_stream() of the concatenated unlimited clips, bit for bit, and `pcm` is made from
+        it.  The limiter looks ahead, so it hands samples out D = look-ahead + 5 samples late (53 samples, 1.66 ms at 32 kHz): the
+        number and order of the clips stay, the text's first clip is D samples shorter and its final clip, which flushes the
+        limiter, D longer; a chunk shorter than D gives a clip with empty audio_data.  audio_len_s counts the samples handed out.
+        Subtitle times are unchanged: the audio runs D / samplerate late against them.  Each clip carries limited (the limiter has
+        acted on the stream so far), dbtp_in (the highest true peak of the unlimited stream so far) and gain_min (the smallest gain
+        among its samples), and no dbtp: there is no trim and the output's true peak is not measured; 4.23 states by how much it
+        can pass the ceiling.  With loudness= as well the leveller's own peak limit is off and the limiter holds the ceiling, as
+        for clips."""
+        loudness, loudness_seed, true_peak = _check_loudness(loudness), _check_loudness_seed(loudness_seed), _check_true_peak(true_peak)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -1078,7 +1102,8 @@ class TTS:
                 audio_len_s, cur_text_l, last_end_s = 0.0, 0, 0
                 cuts = cut_text(text, cut_minlen)
                 resampler = None if track is None else TrackResampler(track, self.samplerate, dev)
-                leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev)
+                leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev, true_peak is not None)
+                limiter = None if true_peak is None else self._limiter(true_peak, dev)
                 for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
@@ -1127,12 +1152,16 @@ class TTS:
                                     new_subtitles[-1]["end_s"] = None
                             if leveller is not None:
                                 audio = leveller.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
+                            if limiter is not None:
+                                audio = limiter.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             pcm = None if resampler is None else resampler.push(audio, flush=is_final and i == len(cuts) - 1)
                             audio = audio.float().cpu().numpy()
                         audio_len_s += len(audio) / self.samplerate
                         clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
                         if leveller is not None:
                             _with_level(clip, leveller.rec)
+                        if limiter is not None:
+                            _with_stream_limit(clip, limiter.rec)
                         if resampler is not None:
                             clip.pcm, clip.pcm_rate = pcm, track.rate
                         yield clip
@@ -1146,9 +1175,16 @@ class TTS:
                     pass
                 self._empty_cache()
 
-    def _leveller(self, target, seed, dev):
+    def _leveller(self, target, seed, dev, held=False):
+        """held: a stream limiter follows and holds the ceiling, so the leveller's own peak limit is off (the clip path's rule)"""
         from .level import StreamLeveller
+        if held:
+            return StreamLeveller(target, self.samplerate, dev, seed=seed, peak_limit=float("inf"))
         return StreamLeveller(target, self.samplerate, dev, seed=seed)
+
+    def _limiter(self, ceiling, dev):
+        from .limiter import StreamLimiter
+        return StreamLimiter(ceiling, self.samplerate, dev)
 
     def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
                              is_cut_text=True, cut_minlen=10, cut_mute=0.4,
@@ -1157,7 +1193,8 @@ class TTS:
                                                  "、": 0.8, "・": 0.8},
                              stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                              temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                             sovits_model=None, debug=True, slots=None, seed=None, track=None, loudness=None, loudness_seed=None):
+                             sovits_model=None, debug=True, slots=None, seed=None, track=None, loudness=None, loudness_seed=None,
+                             true_peak=None):
         """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
         `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
         requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
@@ -1181,7 +1218,11 @@ class TTS:
         loudness / loudness_seed: as in `infer_stream`, one value or one per text, None allowed per text (a wrong length raises
         ValueError).  Every text with a value has its own leveller, enqueued between the chunk's epilogue and the track's push, in
         place with the chunk's length read on the device: the loop still waits for nothing, a text's audio does not depend on its
-        neighbours, and a text without a value gets the clips it gets today."""
+        neighbours, and a text without a value gets the clips it gets today.
+
+        true_peak: as in `infer_stream`, one value or one per text, None allowed per text (a wrong length raises ValueError).
+        Every text with a value has its own limiter, enqueued behind the leveller and in front of the track's push, which then
+        reads its length from the limiter's record on the device: the loop still waits for nothing."""
         with self._infer_lock:
             vq, gen = None, None
             try:
@@ -1192,6 +1233,7 @@ class TTS:
                     return
                 loudness = [_check_loudness(v) for v in slot_sampling.per_request("loudness", loudness, n)]
                 loudness_seed = [_check_loudness_seed(v) for v in slot_sampling.per_request("loudness_seed", loudness_seed, n)]
+                true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, n)]
                 speed = slot_sampling.per_request("speed", speed, n)
                 noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
                 if not all(s > 0 for s in speed):
@@ -1225,7 +1267,9 @@ class TTS:
                     lines.append(_TextLine(text, cut_text(text, cut_minlen), self._ge_for(spk_audio_paths[t], sovits_model),
                                            overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t,
                                            None if track is None else TrackResampler(track, self.samplerate, dev),
-                                           None if loudness[t] is None else self._leveller(loudness[t], loudness_seed[t], dev)))
+                                           None if loudness[t] is None else
+                                           self._leveller(loudness[t], loudness_seed[t], dev, true_peak[t] is not None),
+                                           None if true_peak[t] is None else self._limiter(true_peak[t], dev)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1346,6 +1390,8 @@ class TTS:
         clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
         if handle.level is not None:
             _with_level(clip, handle.level)
+        if handle.limit is not None:
+            _with_stream_limit(clip, handle.limit)
         if pcm:
             clip.pcm, clip.pcm_rate = pcm[0], ln.emitter.track.fmt.rate
         return clip

@@ -584,6 +584,49 @@ int gsv_limiter(const float* x, size_t n_x, const gsv_limiter_clip* clips, int n
 int gsv_limiter_host(const float* x, size_t n_x, const gsv_limiter_clip* clips, int n_clips, int lookahead, int release,
                      float* out, gsv_limiter_record* records, void* work, size_t work_bytes);
 
+/* Stream limiter: the limiter above for a stream that arrives in pushes (csrc/limstream.h).  The output is
+ * stages e .. y1 of gsv_limiter applied to the whole stream as one clip, y[n] = g[n] x[n], with three differences: no trim; no
+ * "a clip under its ceiling is not touched"; instead a window whose L values of r are all exactly 1 gives g = 1 and the sample
+ * is copied.  y[n] is final once x[n + L + 5] has arrived: the limiter delays the stream by D = lookahead + 5 samples.  After N
+ * samples max(0, N - D) outputs have been emitted (a push may emit none); a flush emits the rest (zeros behind the end of x,
+ * c = 1 behind the end) and returns the state to fresh.  The emitted bytes never depend on how the stream was cut into pushes:
+ * the release is computed on 1024-sample tiles aligned to the stream index with the clip kernels' operations, and a tile a
+ * push leaves unfinished is redone from its h, so for a stream that is limited somewhere the output equals fl(g x) with g the
+ * stage array of gsv_limiter for the same samples as one clip, bit for bit (at a look-ahead with fl(L fl(1/L)) == 1).  A sample
+ * whose envelope is not finite needs gain 1 and is copied (GSV_LIMS_NONFINITE); such envelopes are kept out of the peaks.
+ * |y[n]| <= T (1 + 2^-22); the TRUE peak of y may exceed T by what the gain smoothing moves peaks between the samples.
+ *   state: caller-owned, gsv_limstream_state_bytes bytes (0: lookahead outside 1..4096 or release outside 1..2^24), 16-byte
+ *   aligned, made by gsv_limstream_init: a header, the constants, a ring of the newest lookahead + 11 samples, h of the open
+ *   tile, r of the last lookahead - 1 outputs, the chain's start, and the per-push scratch of the tile ends.
+ *   gsv_limstream_out_capacity: n_cap + D, the floats `out` must hold (0: bad arguments).
+ *   gsv_limstream_push: chunk fp32 [n_cap], n_cap 0..2^20 (NULL allowed at 0); n_dev NULL or a device int32 holding the real
+ *   length (clamped to 0..n_cap); out != chunk; rec (device, 8-byte aligned).  Three launches whatever the length, nothing
+ *   allocated, nothing read by the host.  A state gsv_limstream_init did not make is not read through: flags -1.
+ *   gsv_limstream_init_host / gsv_limstream_push_host: the same over HOST memory from the same scalar routines -- the CPU path
+ *   and the device's oracle (device samples and records equal the host's); they need no GPU.
+ * GSV_ERR_ARG: a null pointer, a size that is negative or above 2^20, out == chunk, a state that is too small or misaligned, a
+ * misaligned record, a ceiling outside -200..0 dBTP, a bad look-ahead / release. */
+typedef struct {
+    int32_t emitted;            /* samples this push wrote to out: its address serves as the next stage's n_dev */
+    int16_t flags, lookahead;
+    float peak_in;              /* max finite e over the samples emitted by this push (0: none) */
+    float peak_run;             /* ... by the stream so far */
+    float min_gain;             /* min g over the samples emitted by this push (1: none) */
+    int32_t release;
+    int64_t total;              /* samples emitted by the stream so far */
+} gsv_limstream_record;
+#define GSV_LIMS_LIMITED 1          /* a gain below 1 among this push's samples */
+#define GSV_LIMS_LIMITED_EVER 2     /* ... among the stream's so far */
+#define GSV_LIMS_NONFINITE 4        /* an envelope that is not finite among this push's samples */
+size_t gsv_limstream_state_bytes(int lookahead, int release);
+size_t gsv_limstream_out_capacity(int n_cap, int lookahead);
+int gsv_limstream_init(void* state, size_t bytes, float ceiling_db, int lookahead, int release, void* stream);
+int gsv_limstream_push(void* state, const float* chunk, int n_cap, const int32_t* n_dev, int flush, float* out,
+                       gsv_limstream_record* rec, void* stream);
+int gsv_limstream_init_host(void* state, size_t bytes, float ceiling_db, int lookahead, int release);
+int gsv_limstream_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
+                            gsv_limstream_record* rec);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
