@@ -3,7 +3,8 @@
 Package layout (DESIGN.md):  csrc/ + lib/  HIP kernels and the C ABI (include/gsv_tts_hip.h);
 t2s.py / sovits.py  host mirrors of the reference's Text2SemanticDecoder / SynthesizerTrn;
 loader.py  checkpoint formats;  tts.py  the `TTS` facade;  track.py  s16 packets for a real-time track;  loudness.py  BS.1770 loudness
-and normalisation;  limiter.py  true peak and the look-ahead limiter;  scheduler.py  utterance sharding
+and normalisation;  limiter.py  true peak and the look-ahead limiter;  eq.py  the parametric equaliser;
+scheduler.py  utterance sharding
 over the GPUs of a node;  synth.py  deterministic synthetic weights/inputs.
 """
 from . import synth  # noqa: F401

@@ -42,6 +42,7 @@ EXPORTS = [
     "gsv_limiter_work_bytes", "gsv_limiter", "gsv_limiter_host",
     "gsv_limstream_state_bytes", "gsv_limstream_out_capacity", "gsv_limstream_init", "gsv_limstream_push", "gsv_limstream_init_host",
     "gsv_limstream_push_host",
+    "gsv_eq_work_bytes", "gsv_eq", "gsv_eq_host",
 ]
 
 
@@ -186,6 +187,27 @@ LIMS_LIMITED, LIMS_LIMITED_EVER, LIMS_NONFINITE = 1, 2, 4       # GSV_LIMS_*
 LIMS_MAX_CHUNK = 1 << 20                # csrc/limstream.h: samples of one push
 LIM_TILE, LIM_MAX_LOOKAHEAD, LIM_MAX_RELEASE = 1024, 4096, 1 << 24      # csrc/limiter.h: LIM_TILE, LIM_MAX_L, LIM_MAX_R
 
+EQ_MAX_SECTIONS = 6             # GSV_EQ_MAX_SECTIONS
+
+
+class EqClip(ctypes.Structure):
+    """gsv_eq_clip: one clip of gsv_eq; design -1: measure the peaks, copy"""
+    _fields_ = [("offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("design", ctypes.c_int32)]
+
+
+class EqDesign(ctypes.Structure):
+    """gsv_eq_design: per section b0 b1 b2 a1 a2, normalised by a0"""
+    _fields_ = [("n_sections", ctypes.c_int32), ("reserved", ctypes.c_int32), ("coef", (ctypes.c_double * 5) * EQ_MAX_SECTIONS)]
+
+
+class EqRecord(ctypes.Structure):
+    """gsv_eq_record: what gsv_eq found and did per clip"""
+    _fields_ = [("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float), ("sections", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+EQ_EQUALISED, EQ_NONFINITE = 1, 4       # GSV_EQ_*
+EQ_RUN, EQ_SPAN, EQ_CHUNK = 16, 512 * 16, 2 * 512 * 16      # csrc/eq.h: EQ_R, EQ_SPAN, EQ_CHUNK
+
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
 
@@ -313,6 +335,8 @@ def lib():
         "gsv_level_push_host": [vp, vp, i, vp, i, vp, vp],
         "gsv_limiter": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz, vp],
         "gsv_limiter_host": [vp, sz, ctypes.POINTER(LimiterClip), i, i, i, vp, vp, vp, sz],
+        "gsv_eq": [vp, sz, ctypes.POINTER(EqClip), i, ctypes.POINTER(EqDesign), i, vp, vp, vp, sz, vp],
+        "gsv_eq_host": [vp, sz, ctypes.POINTER(EqClip), i, ctypes.POINTER(EqDesign), i, vp, vp, vp, sz],
         "gsv_limstream_init": [vp, sz, ctypes.c_float, i, i, vp],
         "gsv_limstream_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_limstream_init_host": [vp, sz, ctypes.c_float, i, i],
@@ -361,6 +385,8 @@ def lib():
     L.gsv_loudness_work_bytes.restype = sz
     L.gsv_limiter_work_bytes.argtypes = [ctypes.POINTER(LimiterClip), i]
     L.gsv_limiter_work_bytes.restype = sz
+    L.gsv_eq_work_bytes.argtypes = [ctypes.POINTER(EqClip), i, ctypes.POINTER(EqDesign), i]
+    L.gsv_eq_work_bytes.restype = sz
     L.gsv_limstream_state_bytes.argtypes = [i, i]
     L.gsv_limstream_state_bytes.restype = sz
     L.gsv_limstream_out_capacity.argtypes = [i, i]

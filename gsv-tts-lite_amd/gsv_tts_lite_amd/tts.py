@@ -103,6 +103,7 @@ class AudioClip:
                                     # `limited` then says whether the limiter had to act
         self.dbtp_in = None         # a clip of a stream made with true_peak=: the highest true peak in dBTP of the UNLIMITED stream so
         self.gain_min = None        # far, and the smallest gain among this clip's samples; `limited`: the limiter has acted so far
+        self.eq = None              # a clip made with eq= (or by equalised()): the eq.EqRecord -- peak_in, peak_out, sections
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -149,7 +150,20 @@ class AudioClip:
         lufs / gain / limited say what was measured and done (loudness.normalise)"""
         from . import loudness
         audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
-        return _with_loudness(AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text), rec)
+        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
+        out.eq = self.eq
+        return _with_loudness(out, rec)
+
+    def equalised(self, eq="voice") -> "AudioClip":
+        """a new clip through the equaliser `eq` -- an eq.EQ or a preset name (eq.py) --, same subtitles and text; its
+        `eq` is the eq.EqRecord: the peak before and after, which boosts may lift above 1.0 (limited_to() holds a ceiling)"""
+        from . import eq as eqm
+        if not isinstance(eq, (str, eqm.EQ)):
+            raise ValueError("eq: a preset name (%s) or an eq.EQ, not %r" % (", ".join(eqm.PRESETS), type(eq).__name__))
+        audio, rec = eqm.equalise(self.audio_data, self.samplerate, eq)
+        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
+        out.eq = rec
+        return out
 
     def true_peak(self) -> float:
         """the true peak of audio_data in dBTP (limiter.true_peak: the largest magnitude of the clip oversampled 4x, measured on
@@ -163,7 +177,7 @@ class AudioClip:
         from . import limiter
         audio, rec = limiter.limit(self.audio_data, self.samplerate, ceiling_db)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.lufs, out.gain = self.lufs, self.gain
+        out.lufs, out.gain, out.eq = self.lufs, self.gain, self.eq
         return _with_true_peak(out, rec)
 
     def _save_wav(self, save_path):
@@ -179,8 +193,9 @@ def _with_loudness(clip, rec):
     return clip
 
 
-def _with_records(clip, rec, lim):
-    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim) or both"""
+def _with_records(clip, rec, lim, eqr=None):
+    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr) or several of them"""
+    clip.eq = eqr
     if rec is not None:
         _with_loudness(clip, rec)
     return clip if lim is None else _with_true_peak(clip, lim)
@@ -194,6 +209,14 @@ def _with_true_peak(clip, rec):
 def _check_true_peak(v):
     from . import limiter
     return limiter.check_ceiling(v)
+
+
+def _check_eq(v, rate):
+    """an eq= value: None, a preset name or an eq.EQ -> None (also for an EQ that is the identity) or the EQ"""
+    if v is None:
+        return None
+    from . import eq
+    return eq.resolve(v, rate)
 
 
 def _with_level(clip, rec):
@@ -870,8 +893,13 @@ class TTS:
     @torch.inference_mode()
     def infer(self, spk_audio_path, prompt_audio_path, prompt_audio_text, text, return_subtitles=False, top_k=15,
               top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-              sovits_model=None, loudness=None, true_peak=None):
-        """loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
+              sovits_model=None, loudness=None, true_peak=None, eq=None):
+        """eq: None, a preset name ("voice": the three filters of the reference WebUI's enhance_audio) or an eq.EQ: the clip that
+        would have been returned -- after the peak rule, trailing 0.2 s of zeros included -- goes through that equaliser on the
+        device before the download (eq.py), ahead of loudness= and true_peak= as in the reference's chain; the clip
+        then carries `eq`, the record with the peak before and after.  Nothing clamps that peak: true_peak= holds a ceiling.
+
+        loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
         peak rule, trailing 0.2 s of zeros included -- is measured and scaled to it on the device before the download
         (loudness.py); the clip then carries lufs (before the gain), gain and limited.
 
@@ -879,7 +907,7 @@ class TTS:
         by the look-ahead limiter on the device (limiter.py) and carries dbtp (its true peak behind the limiter) and
         limited (the limiter acted).  With loudness= as well the gain to the target is applied whatever the peak becomes, and the
         limiter then holds the ceiling: the loudness that comes out is what the limiter leaves."""
-        loudness, true_peak = _check_loudness(loudness), _check_true_peak(true_peak)
+        loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -915,10 +943,10 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
-                if loudness is not None or true_peak is not None:
-                    audio, rec, lim = self._finish_on_device(audio.float(), loudness, true_peak)
+                if loudness is not None or true_peak is not None or eq is not None:
+                    audio, rec, lim, eqr = self._finish_on_device(audio.float(), loudness, true_peak, eq)
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text),
-                                         rec, lim)
+                                         rec, lim, eqr)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -928,21 +956,28 @@ class TTS:
             finally:
                 self._empty_cache()
 
-    def _finish_on_device(self, audio, target, ceiling=None):
-        """the tail of infer / infer_vc with loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1): dividing by 1 is
-        exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_loudness
-        call (target) and one gsv_limiter call (ceiling) over the finished clip in place, their records written behind the samples:
-        ONE download carries all -> (numpy samples, loudness record or None, limiter record or None).  Ahead of the limiter the
-        gain to the target is applied with no peak limit: the limiter holds the ceiling."""
+    def _finish_on_device(self, audio, target, ceiling=None, eq=None):
+        """the tail of infer / infer_vc with eq=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1): dividing by
+        1 is exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_eq
+        call (eq), one gsv_loudness call (target) and one gsv_limiter call (ceiling) over the finished clip in place, their records
+        written behind the samples: ONE download carries all -> (numpy samples, loudness record or None, limiter record or None,
+        eq record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
+        ceiling."""
+        from . import eq as eqm
         from . import limiter as lm
         from . import loudness as ld
         if audio.numel():
             audio = audio / audio.abs().max().clamp(min=1)
         n = audio.numel() + int(0.2 * self.samplerate)
         words = (ld.RECORD_BYTES // 4 if target is not None else 0) + (lm.RECORD_BYTES // 4 if ceiling is not None else 0)
+        eq_words = eqm.RECORD_BYTES // 4 if eq is not None else 0              # in front of the other two: 16 bytes keep their alignment
+        words += eq_words
         tail = (n + 1) // 2 * 2 - audio.numel() + words                        # zeros to n, to an 8-byte boundary, the records
         buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
         at = buf.numel() - words
+        if eq is not None:
+            eqm.run_packed(buf[:n], [0], [n], [0], [eqm.design(eq, self.samplerate)], buf[:n], buf[at: at + eq_words].view(torch.uint8))
+        eqr_at, at = at, at + eq_words
         if target is not None:
             ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0 if ceiling is None else math.inf, buf[:n],
                           buf[at: at + ld.RECORD_BYTES // 4].view(torch.uint8))
@@ -952,16 +987,17 @@ class TTS:
         host = buf.cpu().numpy()
         rec = ld.records(host[at: at + ld.RECORD_BYTES // 4].view(np.uint8))[0] if target is not None else None
         lim = lm.records(host[host.size - lm.RECORD_BYTES // 4:].view(np.uint8))[0] if ceiling is not None else None
-        return host[:n], rec, lim
+        eqr = eqm.records(host[eqr_at: eqr_at + eq_words].view(np.uint8))[0] if eq is not None else None
+        return host[:n], rec, lim, eqr
 
     @torch.inference_mode()
     def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
-                 loudness=None, true_peak=None):
+                 loudness=None, true_peak=None, eq=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
         decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
-        loudness, true_peak: as in infer."""
-        loudness, true_peak = _check_loudness(loudness), _check_true_peak(true_peak)
-        finish = loudness is not None or true_peak is not None
+        loudness, true_peak, eq: as in infer."""
+        loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
+        finish = loudness is not None or true_peak is not None or eq is not None
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -979,7 +1015,7 @@ class TTS:
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
                 if finish:
-                    audio, rec, lim = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak)
+                    audio, rec, lim, eqr = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq)
                 else:
                     audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
@@ -987,7 +1023,7 @@ class TTS:
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
                 if finish:
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
-                                                   prompt_audio_text), rec, lim)
+                                                   prompt_audio_text), rec, lim, eqr)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1428,7 +1464,7 @@ class TTS:
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
-                      initial_suppression_steps=0, loudness=None, true_peak=None):
+                      initial_suppression_steps=0, loudness=None, true_peak=None, eq=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
 
@@ -1453,7 +1489,12 @@ class TTS:
         true_peak: None, a ceiling in dBTP <= 0 for every text, or one value or None per TEXT (a wrong length raises ValueError).
         The finished clips of the texts with a value -- behind the gain to their loudness target, which is then applied whatever
         the peak becomes -- are held under it in ONE packed gsv_limiter call (limiter.py) and carry dbtp and
-        limited, as in infer."""
+        limited, as in infer.
+
+        eq: None, a preset name or an eq.EQ for every text, or a list with one of those per TEXT (a wrong length raises
+        ValueError; a bare list of eq.Band objects is not an equaliser: wrap it in eq.EQ).  The finished clips of the texts with
+        one go through their equalisers in ONE packed gsv_eq call (eq.py) ahead of the loudness call, the distinct
+        designs passed once, and carry `eq`, as in infer.  A text with None comes back exactly as without the parameter."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
@@ -1467,6 +1508,12 @@ class TTS:
                     true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, len(texts))]
                     if all(v is None for v in true_peak):
                         true_peak = None
+                if eq is not None:
+                    if isinstance(eq, (list, tuple)) and len(eq) != len(texts):
+                        raise ValueError("eq has %d entries for %d requests" % (len(eq), len(texts)))
+                    eq = [_check_eq(v, self.samplerate) for v in (eq if isinstance(eq, (list, tuple)) else [eq] * len(texts))]
+                    if all(v is None for v in eq):
+                        eq = None
                 segmented = slot_sampling.is_sequence(speed) or slot_sampling.is_sequence(noise_scale)
                 if segmented:   # one value per text: the lengths are checked before any device work
                     speed = slot_sampling.per_request("speed", speed, len(texts))
@@ -1650,6 +1697,13 @@ class TTS:
                     a = np.concatenate(parts) if parts else np.zeros(0, np.float32)
                     subtitles = sub.cat_subtitles(*sparts) if return_subtitles else []
                     clips.append(AudioClip(self.audio_queue, a, self.samplerate, len(a) / self.samplerate, subtitles, t))
+                if eq is not None:          # one packed call over the texts that asked, ahead of the loudness call
+                    from . import eq as eqm
+                    pick = [i for i, v in enumerate(eq) if v is not None]
+                    shaped, recs = eqm.equalise([clips[i].audio_data for i in pick], self.samplerate, [eq[i] for i in pick], device=dev)
+                    for i, a, rec in zip(pick, shaped, recs):
+                        clips[i].audio_data = a
+                        clips[i].eq = rec
                 if loudness is not None:    # one packed call over the texts that asked
                     from . import loudness as ld
                     held = [true_peak is not None and true_peak[i] is not None for i in range(len(clips))]

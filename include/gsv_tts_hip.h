@@ -627,6 +627,48 @@ int gsv_limstream_init_host(void* state, size_t bytes, float ceiling_db, int loo
 int gsv_limstream_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
                             gsv_limstream_record* rec);
 
+/* Equaliser: n_clips clips of one packed fp32 buffer, each through one of n_designs cascades of 1 to 6 second-order sections
+ * (csrc/eq.h).  Per section, in list order, from zero state, in fp64 (transposed direct form II):
+ *   y = b0 x + z0;  z0 = b1 x - a1 y + z1;  z1 = b2 x - a2 y;
+ * fp64 between the sections; the last section's output is rounded once to fp32, saturating at +-FLT_MAX.  Same length out as in.
+ *   designs [n_designs] (HOST memory in both entries): per section b0 b1 b2 a1 a2, normalised by a0.  Whoever designs the
+ *   sections needs the sampling rate; this call does not.
+ *   x: fp32 [n_x]; clip c is x[offset, offset + n_samples), mono; the clips do not overlap.  design: an index into designs,
+ *   or -1 for a clip whose peaks are measured and whose samples are copied.
+ *   out: x (in place) or a second buffer of n_x floats; only [offset, offset + n_samples) of each clip is written.
+ *   records [n_clips]: peak_in = max |x|, peak_out = max |y| (nothing clamps y: boosts may lift it above 1), the sections run
+ *   and flags.  A clip holding a NaN or an infinity (GSV_EQ_NONFINITE) comes back bit for bit, sections 0, peak_out = peak_in
+ *   = that NaN or infinity; so does a clip with design -1, flags 0.  An empty clip is legal.
+ *   work: caller-owned, gsv_eq_work_bytes(clips, n_clips, designs, n_designs) bytes (0: bad arguments), 16-byte aligned.
+ *   gsv_eq: x, out, records and work are DEVICE memory, clips and designs HOST memory.  One small upload (the clip rows, the
+ *   coefficients, the scan's matrices) and at most four launches on `stream`; nothing allocated, nothing read back by the host.
+ *   gsv_eq_host: the same over HOST memory from the same scalar routines -- the CPU path and the device's oracle (device
+ *   records and samples equal the host's bit for bit); it needs no GPU.
+ * GSV_ERR_ARG: a null pointer, a bad clip or design count (1..65535 clips, 0..65535 designs), a design index outside the
+ * designs, a clip outside [0, n_x), a section count outside 1..6, a coefficient that is not finite, a section whose poles are
+ * not inside the unit circle (it needs |a2| < 1 and |a1| < 1 + a2), a workspace that is too small or misaligned. */
+#define GSV_EQ_MAX_SECTIONS 6
+typedef struct {
+    int64_t offset;         /* first sample of the clip in x */
+    int32_t n_samples;
+    int32_t design;         /* index into designs; -1: measure the peaks, copy */
+} gsv_eq_clip;
+typedef struct {
+    int32_t n_sections, reserved;
+    double coef[GSV_EQ_MAX_SECTIONS][5];    /* b0 b1 b2 a1 a2 */
+} gsv_eq_design;
+typedef struct {
+    float peak_in, peak_out;
+    int32_t sections, flags;
+} gsv_eq_record;
+#define GSV_EQ_EQUALISED 1      /* the sections were run over the clip */
+#define GSV_EQ_NONFINITE 4      /* a NaN or an infinity among the samples */
+size_t gsv_eq_work_bytes(const gsv_eq_clip* clips, int n_clips, const gsv_eq_design* designs, int n_designs);
+int gsv_eq(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, const gsv_eq_design* designs, int n_designs,
+           float* out, gsv_eq_record* records, void* work, size_t work_bytes, void* stream);
+int gsv_eq_host(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, const gsv_eq_design* designs, int n_designs,
+                float* out, gsv_eq_record* records, void* work, size_t work_bytes);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
