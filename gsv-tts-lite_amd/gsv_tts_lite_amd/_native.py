@@ -43,6 +43,7 @@ EXPORTS = [
     "gsv_limstream_state_bytes", "gsv_limstream_out_capacity", "gsv_limstream_init", "gsv_limstream_push", "gsv_limstream_init_host",
     "gsv_limstream_push_host",
     "gsv_eq_work_bytes", "gsv_eq", "gsv_eq_host",
+    "gsv_eqstream_state_bytes", "gsv_eqstream_init", "gsv_eqstream_push", "gsv_eqstream_init_host", "gsv_eqstream_push_host",
 ]
 
 
@@ -208,6 +209,16 @@ class EqRecord(ctypes.Structure):
 EQ_EQUALISED, EQ_NONFINITE = 1, 4       # GSV_EQ_*
 EQ_RUN, EQ_SPAN, EQ_CHUNK = 16, 512 * 16, 2 * 512 * 16      # csrc/eq.h: EQ_R, EQ_SPAN, EQ_CHUNK
 
+
+class EqstreamRecord(ctypes.Structure):
+    """gsv_eqstream_record: what one gsv_eqstream_push emitted and found"""
+    _fields_ = [("emitted", ctypes.c_int32), ("flags", ctypes.c_int32), ("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float),
+                ("peak_in_run", ctypes.c_float), ("peak_out_run", ctypes.c_float), ("total", ctypes.c_int64)]
+
+
+EQS_EQUALISED, EQS_NONFINITE_EVER, EQS_NONFINITE = 1, 2, 4      # GSV_EQS_*
+EQS_MAX_CHUNK = 1 << 20                 # csrc/eqstream.h: samples of one push
+
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
 
@@ -341,6 +352,10 @@ def lib():
         "gsv_limstream_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_limstream_init_host": [vp, sz, ctypes.c_float, i, i],
         "gsv_limstream_push_host": [vp, vp, i, vp, i, vp, vp],
+        "gsv_eqstream_init": [vp, sz, ctypes.POINTER(EqDesign), vp],
+        "gsv_eqstream_push": [vp, vp, i, vp, i, vp, vp, vp],
+        "gsv_eqstream_init_host": [vp, sz, ctypes.POINTER(EqDesign)],
+        "gsv_eqstream_push_host": [vp, vp, i, vp, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -387,6 +402,8 @@ def lib():
     L.gsv_limiter_work_bytes.restype = sz
     L.gsv_eq_work_bytes.argtypes = [ctypes.POINTER(EqClip), i, ctypes.POINTER(EqDesign), i]
     L.gsv_eq_work_bytes.restype = sz
+    L.gsv_eqstream_state_bytes.argtypes = []
+    L.gsv_eqstream_state_bytes.restype = sz
     L.gsv_limstream_state_bytes.argtypes = [i, i]
     L.gsv_limstream_state_bytes.restype = sz
     L.gsv_limstream_out_capacity.argtypes = [i, i]

@@ -7,6 +7,7 @@ list of them in one call, from zero state, in fp64, rounded once to fp32:
     clips, recs = equalise([a, b, c], 32000, e)                # or one EQ / preset name / None per clip
     recs[0].peak_in, recs[0].peak_out, recs[0].sections
     h = response(e, 32000, [100.0, 1000.0])                    # complex fp64, from the coefficients
+    s = StreamEQ("voice", 32000, "cuda"); y = s.push(chunk)    # a stream in pushes: the same bytes however it is cut
 
 On a GPU device a call is `gsv_eq` (one small upload, at most four launches); on "cpu" the host twin `gsv_eq_host` runs the same
 scalar routines and gives the same bits.  Nothing clamps the output: boosts may lift the peak above 1.0 and the record says so;
@@ -277,3 +278,128 @@ def equalise(clips, rate, eq, device=None):
             host = out.cpu().numpy() if host is None else host
             res.append(host[o:o + n].reshape(np.shape(c)).copy())
     return (res[0], recs[0]) if single else (res, recs)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# streams (csrc/eqstream.h)
+# ----------------------------------------------------------------------------------------------------------------------
+_SREC = np.dtype([("emitted", "<i4"), ("flags", "<i4"), ("peak_in", "<f4"), ("peak_out", "<f4"), ("peak_in_run", "<f4"),
+                  ("peak_out_run", "<f4"), ("total", "<i8")])
+assert _SREC.itemsize == ctypes.sizeof(N.EqstreamRecord)
+STREAM_RECORD_BYTES = _SREC.itemsize
+
+
+class EqStreamRecord:
+    """emitted: samples the push handed out (as many as it took); total: samples of the stream so far; peak_in / peak_out: max |x|
+    and max |y| over the push's finite samples (np.float32, 0 for none), peak_in_run / peak_out_run: over the stream's so far
+    (nothing clamps them: boosts may lift peak_out_run above 1.0); equalised: the record of a live state; nonfinite: a NaN or an
+    infinity among this push's samples (it ran through the filter as 0.0 and was copied to the output), nonfinite_ever: among the
+    stream's so far"""
+
+    __slots__ = ("emitted", "total", "peak_in", "peak_out", "peak_in_run", "peak_out_run", "equalised", "nonfinite", "nonfinite_ever")
+
+    def __init__(self, emitted, flags, peak_in, peak_out, peak_in_run, peak_out_run, total):
+        self.emitted, self.total = int(emitted), int(total)
+        self.peak_in, self.peak_out = np.float32(peak_in), np.float32(peak_out)
+        self.peak_in_run, self.peak_out_run = np.float32(peak_in_run), np.float32(peak_out_run)
+        self.equalised = bool(flags & N.EQS_EQUALISED)
+        self.nonfinite = bool(flags & N.EQS_NONFINITE)
+        self.nonfinite_ever = bool(flags & N.EQS_NONFINITE_EVER)
+
+    def __repr__(self):
+        return "EqStreamRecord(emitted=%d, total=%d, peak_in=%r, peak_out=%r, peak_in_run=%r, peak_out_run=%r, nonfinite=%r, nonfinite_ever=%r)" % (
+            self.emitted, self.total, float(self.peak_in), float(self.peak_out), float(self.peak_in_run), float(self.peak_out_run),
+            self.nonfinite, self.nonfinite_ever)
+
+
+def stream_record(raw):
+    """the 32 record bytes (a tensor on any device, or a numpy array of them) -> EqStreamRecord"""
+    raw = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    return EqStreamRecord(*np.frombuffer(raw.tobytes()[:STREAM_RECORD_BYTES], dtype=_SREC)[0].tolist())
+
+
+class StreamEQ:
+    """One stream through the equaliser `eq` -- a preset name or an EQ -- at `rate`.  push(x, flush) -> float32 numpy,
+    as many samples as went in: an equaliser is causal, so there is no delay, and a flush hands out nothing extra; it ends the
+    stream, and the next push starts a fresh one with the same design.  The samples never depend on how the stream was cut into
+    pushes: concatenated they are `equalise` of the concatenated input, bit for bit.  A NaN or an infinity runs through the filter
+    as 0.0 and is copied to the output.  On a GPU device a push is the four launches of `gsv_eqstream_push`; on "cpu" the host
+    twin runs the same scalar routines and gives the same bytes."""
+
+    def __init__(self, eq, rate: int, device="cpu"):
+        self.rate = _check_rate(rate)
+        self.eq = resolve(eq, self.rate)
+        if self.eq is None:
+            raise ValueError("a stream equaliser needs an equaliser that is not the identity")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        _, des = _tables([], [], [], [design(self.eq, self.rate)])
+        L = N.lib()
+        nbytes = L.gsv_eqstream_state_bytes()
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                N.check(L.gsv_eqstream_init(self.state.data_ptr(), nbytes, des, N.current_stream_ptr(self.device)))
+        else:
+            N.check(L.gsv_eqstream_init_host(self.state.data_ptr(), nbytes, des))
+        self._rec = None        # the last push's record
+
+    @property
+    def on_device(self) -> bool:
+        return self.device.type == "cuda"
+
+    def enqueue(self, chunk_ptr: int, n_cap: int, n_dev_ptr, flush: bool, out_ptr: int, rec_ptr: int):
+        """the raw device call on the current stream: nothing is read back (ChunkEmitter's use); out_ptr may be chunk_ptr"""
+        N.check(N.lib().gsv_eqstream_push(self.state.data_ptr(), chunk_ptr or None, int(n_cap), n_dev_ptr, int(bool(flush)),
+                                          out_ptr or None, rec_ptr, N.current_stream_ptr(self.device)))
+
+    def _push_once(self, x: torch.Tensor, flush: bool):
+        n = int(x.numel())
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        rec = torch.empty(STREAM_RECORD_BYTES // 8, dtype=torch.int64, device=self.device)      # 8-byte aligned
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                self.enqueue(x.data_ptr(), n, None, flush, out.data_ptr(), rec.data_ptr())
+        else:
+            N.check(N.lib().gsv_eqstream_push_host(self.state.data_ptr(), x.data_ptr() or None, n, None, int(bool(flush)),
+                                                   out.data_ptr() or None, rec.data_ptr()))
+        return out, rec
+
+    def push_tensor(self, x: torch.Tensor, flush: bool = False) -> torch.Tensor:
+        """x on the equaliser's device -> the equalised samples, a new fp32 tensor there of x's length.  The record is read, so the
+        call waits for the push.  Input longer than one push may be (2^20 samples) goes in as several, which changes no byte; `rec`
+        is then the last one's."""
+        x = x.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        parts = []
+        cuts = list(range(0, int(x.numel()), N.EQS_MAX_CHUNK)) or [0]
+        for k, at in enumerate(cuts):
+            out, rec = self._push_once(x[at: at + N.EQS_MAX_CHUNK], flush and k + 1 == len(cuts))
+            self._rec = stream_record(rec.view(torch.uint8))
+            parts.append(out[: self._rec.emitted])
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def push(self, x, flush: bool = False) -> np.ndarray:
+        return self.push_tensor(torch.as_tensor(x), flush).cpu().numpy()
+
+    @property
+    def rec(self):
+        """the last push's EqStreamRecord (None before the first push)"""
+        return self._rec
+
+
+def equalise_stream(x, rate, eq, cuts=None, device=None):
+    """the whole signal equalised as one stream on the CPU's host twin (the GPU gives the same bytes: name a device to run there)
+    -> (float32 numpy, the last push's EqStreamRecord).  cuts: the lengths of the pushes to cut it into (they must add up to the
+    signal's; an empty push is legal), default one push; the last one flushes.  However it is cut, the samples are
+    `equalise(x, rate, eq)`'s."""
+    x = np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
+    cuts = [len(x)] if cuts is None else [int(c) for c in cuts]
+    if any(c < 0 for c in cuts) or sum(cuts) != len(x) or not cuts:
+        raise ValueError("eq: cuts of %r for %d samples" % (cuts, len(x)))
+    st = StreamEQ(eq, rate, torch.device("cpu") if device is None else device)
+    parts, at = [], 0
+    for k, c in enumerate(cuts):
+        parts.append(st.push(x[at: at + c], flush=k + 1 == len(cuts)))
+        at += c
+    return np.concatenate(parts), st.rec

@@ -11,7 +11,8 @@ compute on this path and no CPU fallback.
 the device, and the samples reach the host by one asynchronous copy behind a handle.  With a `track` (track.TrackResampler) the s16
 packets of a real-time track are made behind it by `gsv_track_push`, which reads the chunk's length from the emit record on the
 device, and travel in the same copy.  With a `level` (level.StreamLeveller) the emitted samples are levelled in place by
-`gsv_level_push` between the two, the same way: a track then carries levelled audio."""
+`gsv_level_push` between the two, the same way: a track then carries levelled audio.  With an `eq` (eq.StreamEQ) they are equalised
+in place by `gsv_eqstream_push` first of all, so the leveller measures equalised audio as `loudness=` does on clips."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -59,8 +60,10 @@ class ChunkSplicer:
 class _Emitted:
     """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
 
-    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None):
+    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None, eq_at=None):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
+        self._eq_at = eq_at         # with an equaliser: where its record starts in the buffer (fp32 elements)
+        self.eq = None              # and the record itself (eq.EqStreamRecord), once result() has been called
         self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
         self._level_at = level_at   # with a leveller: where its record starts
         self.level = None           # and the record itself (level.LevelRecord), once result() has been called
@@ -79,6 +82,9 @@ class _Emitted:
             host = self._bufs[1]
             n_out, k, h, _ = host[:4].view(torch.int32).tolist()
             self._value = (host[4: 4 + n_out].numpy().copy(), k, h)
+            if self._eq_at is not None:
+                from . import eq
+                self.eq = eq.stream_record(host[self._eq_at: self._eq_at + eq.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
             if self._level_at is not None:
                 from . import level
                 self.level = level.record(host[self._level_at: self._level_at + level.RECORD_BYTES // 4].numpy().view("uint8"))
@@ -118,10 +124,18 @@ class ChunkEmitter:
     leveller (emit -> level -> limit -> track), out of place into its own region of the buffer, the chunk's length read from
     `gsv_stream_emit`'s record on the device; the samples handed out are the ones the limiter emitted with this push -- `delay`
     samples behind the chunk, so the first chunk of a text is that much shorter and the flushing one that much longer --, the
-    track reads them with their number from the limiter's record, and the handle carries that record in `limit`."""
+    track reads them with their number from the limiter's record, and the handle carries that record in `limit`.
 
-    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None):
+    eq: an eq.StreamEQ on the chunks' device, or None.  With one, push() enqueues `gsv_eqstream_push` directly behind
+    `gsv_stream_emit` and in front of the leveller (emit -> eq -> level -> limit -> track), in place on the samples it wrote, their
+    number read from its record on the device; the stages behind read their length from the equaliser's record, which rides
+    8-byte aligned behind the samples in the same buffer and the same copy, and the handle carries it in `eq`.  Its state spans
+    the text like the others', and `flush` ends its stream too.  Without one the buffer's layout and every byte are what they
+    were."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None, eq=None):
         self.overlap, self.search_len, self.track, self.level, self.limit = int(overlap_samples), int(search_len), track, level, limit
+        self.eq = eq
         self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
         self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
 
@@ -149,23 +163,29 @@ class ChunkEmitter:
         used = 4 + n + int(mute_samples)
         lim_cap = 0 if self.limit is None else self.limit.capacity(used - 4)     # the most samples the limiter emits
         pcm_cap = 0 if self.track is None else (self.track.capacity(lim_cap or used - 4) + 1) // 2      # int16 pairs as fp32 elements
-        lrec = 0 if self.level is None else (used & 1) + 10       # the level record, 8-byte aligned, as fp32 elements
-        mrec = 0 if self.limit is None else ((used + lrec) & 1) + 8 + lim_cap      # the limiter's record, 8-byte aligned, and its samples
-        dbuf, hbuf = bufs = self._buffers(used + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
+        erec = 0 if self.eq is None else (used & 1) + 8           # the equaliser's record, 8-byte aligned, as fp32 elements
+        lrec = 0 if self.level is None else ((used + erec) & 1) + 10      # the level record, 8-byte aligned
+        mrec = 0 if self.limit is None else ((used + erec + lrec) & 1) + 8 + lim_cap       # the limiter's record, 8-byte aligned, and its samples
+        dbuf, hbuf = bufs = self._buffers(used + erec + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
                                   int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
                                   self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        pcm_at, level_at, limit_at, n_samples = None, None, None, used - 4
-        src, src_cap, src_len = dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr()       # what the track reads: samples, capacity, length
+        pcm_at, level_at, limit_at, eq_at, n_samples = None, None, None, None, used - 4
+        src, src_cap, src_len = dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr()       # what the next stage reads: samples, capacity, length
+        if self.eq is not None:          # [rec 4 | samples | eq rec 8 (8-byte aligned) | ...]: in place, first of all
+            eq_at = used + (used & 1)
+            self.eq.enqueue(src, n_samples, src_len, flush, src, dbuf[eq_at:].data_ptr())
+            src_len = dbuf[eq_at:].data_ptr()
+            used += erec
         if self.level is not None:       # [rec 4 | samples | level rec 10 (8-byte aligned) | ...]: in place, before the track reads them
             level_at = used + (used & 1)
-            self.level.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
+            self.level.enqueue(dbuf[4:].data_ptr(), n_samples, src_len, flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
             used += lrec
         if self.limit is not None:       # [... | limiter rec 8 (8-byte aligned) | its samples n + delay | ...]: out of place
             limit_at = used + (used & 1)
-            self.limit.enqueue(dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr(), flush, dbuf[limit_at + 8:].data_ptr(),
+            self.limit.enqueue(dbuf[4:].data_ptr(), n_samples, src_len, flush, dbuf[limit_at + 8:].data_ptr(),
                                dbuf[limit_at:].data_ptr())
             src, src_cap, src_len = dbuf[limit_at + 8:].data_ptr(), lim_cap, dbuf[limit_at:].data_ptr()
             used += mrec
@@ -176,4 +196,4 @@ class ChunkEmitter:
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at)
+        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at, eq_at)

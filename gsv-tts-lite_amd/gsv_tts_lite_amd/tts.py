@@ -103,7 +103,8 @@ class AudioClip:
                                     # `limited` then says whether the limiter had to act
         self.dbtp_in = None         # a clip of a stream made with true_peak=: the highest true peak in dBTP of the UNLIMITED stream so
         self.gain_min = None        # far, and the smallest gain among this clip's samples; `limited`: the limiter has acted so far
-        self.eq = None              # a clip made with eq= (or by equalised()): the eq.EqRecord -- peak_in, peak_out, sections
+        self.eq = None              # a clip made with eq= (or by equalised()): the eq.EqRecord -- peak_in, peak_out, sections;
+                                    # a clip of a stream made with eq=: the eq.EqStreamRecord of its push
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -298,15 +299,18 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None, eq=None):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        # the text's own TrackResampler / StreamLeveller / StreamLimiter, or None (without a limiter: the call as it always was)
-        self.emitter = (ChunkEmitter(overlap_samples, track=track, level=level) if limit is None else
-                        ChunkEmitter(overlap_samples, track=track, level=level, limit=limit))
+        # the text's own TrackResampler / StreamLeveller / StreamLimiter / StreamEQ, or None (without a limiter or an equaliser: the
+        # call as it always was)
+        stages = {} if limit is None else {"limit": limit}
+        if eq is not None:
+            stages["eq"] = eq
+        self.emitter = ChunkEmitter(overlap_samples, track=track, level=level, **stages)
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
         self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
@@ -1081,7 +1085,7 @@ class TTS:
                                          "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0, "、": 0.8, "・": 0.8},
                      stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                      temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None, true_peak=None):
+                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None, true_peak=None, eq=None):
         """TTS.py:289-504: generator of AudioClip chunks.  Per text segment the GPT streams cumulative token
         chunks (t2s.infer_stream); every chunk is decoded from the start of the segment with
         decode(stream_mode=True) -- only frames past `valid_start_idx` reach the flow / Generator -- and joined
@@ -1110,8 +1114,17 @@ class TTS:
         acted on the stream so far), dbtp_in (the highest true peak of the unlimited stream so far) and gain_min (the smallest gain
         among its samples), and no dbtp: there is no trim and the output's true peak is not measured; 4.23 states by how much it
         can pass the ceiling.  With loudness= as well the leveller's own peak limit is off and the limiter holds the ceiling, as
-        for clips."""
+        for clips.
+
+        eq: None, a preset name ("voice") or an eq.EQ: the text's audio -- one stream, as for loudness= -- goes through the stream
+        equaliser on the device (eq.StreamEQ) first of all, ahead of the leveller and the limiter as on the clip path:
+        the concatenated audio_data is eq.equalise() of the concatenated unequalised clips, bit for bit, and the leveller measures
+        equalised audio.  An equaliser is causal: no delay, the clips keep their lengths.  Each clip carries `eq`, the
+        eq.EqStreamRecord: the peaks before and after of its samples and of the stream so far, which nothing clamps (peak_out_run
+        may exceed 1.0; true_peak= holds a ceiling), and `total`, the stream's samples so far.  An EQ that is the identity is as
+        no EQ."""
         loudness, loudness_seed, true_peak = _check_loudness(loudness), _check_loudness_seed(loudness_seed), _check_true_peak(true_peak)
+        eq = _check_eq(eq, self.samplerate)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -1140,6 +1153,7 @@ class TTS:
                 resampler = None if track is None else TrackResampler(track, self.samplerate, dev)
                 leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev, true_peak is not None)
                 limiter = None if true_peak is None else self._limiter(true_peak, dev)
+                equaliser = None if eq is None else self._equaliser(eq, dev)
                 for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
@@ -1186,6 +1200,8 @@ class TTS:
                                 last_subtitles_end = len(subtitles) - 1
                                 if not is_final and new_subtitles:
                                     new_subtitles[-1]["end_s"] = None
+                            if equaliser is not None:
+                                audio = equaliser.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             if leveller is not None:
                                 audio = leveller.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             if limiter is not None:
@@ -1194,6 +1210,8 @@ class TTS:
                             audio = audio.float().cpu().numpy()
                         audio_len_s += len(audio) / self.samplerate
                         clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
+                        if equaliser is not None:
+                            clip.eq = equaliser.rec
                         if leveller is not None:
                             _with_level(clip, leveller.rec)
                         if limiter is not None:
@@ -1222,6 +1240,10 @@ class TTS:
         from .limiter import StreamLimiter
         return StreamLimiter(ceiling, self.samplerate, dev)
 
+    def _equaliser(self, eq, dev):
+        from .eq import StreamEQ
+        return StreamEQ(eq, self.samplerate, dev)
+
     def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
                              is_cut_text=True, cut_minlen=10, cut_mute=0.4,
                              cut_mute_scale_map={"…": 2.0, ".": 1.5, "。": 1.5, "?": 1.5, "？": 1.5, "!": 1.5, "！": 1.5,
@@ -1230,7 +1252,7 @@ class TTS:
                              stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                              temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
                              sovits_model=None, debug=True, slots=None, seed=None, track=None, loudness=None, loudness_seed=None,
-                             true_peak=None):
+                             true_peak=None, eq=None):
         """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
         `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
         requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
@@ -1258,7 +1280,12 @@ class TTS:
 
         true_peak: as in `infer_stream`, one value or one per text, None allowed per text (a wrong length raises ValueError).
         Every text with a value has its own limiter, enqueued behind the leveller and in front of the track's push, which then
-        reads its length from the limiter's record on the device: the loop still waits for nothing."""
+        reads its length from the limiter's record on the device: the loop still waits for nothing.
+
+        eq: as in `infer_stream`, None, a preset name or an eq.EQ for every text, or a list with one of those per TEXT (a wrong
+        length raises ValueError; a bare list of eq.Band objects is not an equaliser: wrap it in eq.EQ).  Every text with one has
+        its own equaliser state, enqueued directly behind the chunk's epilogue, in place and in front of the leveller, with the
+        chunk's length read on the device: the loop still waits for nothing, and a text with None gets the clips it gets today."""
         with self._infer_lock:
             vq, gen = None, None
             try:
@@ -1270,6 +1297,9 @@ class TTS:
                 loudness = [_check_loudness(v) for v in slot_sampling.per_request("loudness", loudness, n)]
                 loudness_seed = [_check_loudness_seed(v) for v in slot_sampling.per_request("loudness_seed", loudness_seed, n)]
                 true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, n)]
+                if isinstance(eq, (list, tuple)) and len(eq) != n:
+                    raise ValueError("eq has %d entries for %d requests" % (len(eq), n))
+                eq = [_check_eq(v, self.samplerate) for v in (eq if isinstance(eq, (list, tuple)) else [eq] * n)]
                 speed = slot_sampling.per_request("speed", speed, n)
                 noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
                 if not all(s > 0 for s in speed):
@@ -1305,7 +1335,8 @@ class TTS:
                                            None if track is None else TrackResampler(track, self.samplerate, dev),
                                            None if loudness[t] is None else
                                            self._leveller(loudness[t], loudness_seed[t], dev, true_peak[t] is not None),
-                                           None if true_peak[t] is None else self._limiter(true_peak[t], dev)))
+                                           None if true_peak[t] is None else self._limiter(true_peak[t], dev),
+                                           None if eq[t] is None else self._equaliser(eq[t], dev)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1424,6 +1455,8 @@ class TTS:
             ln.seg, ln.y_overlap, ln.valid_start_idx, ln.chunk_idx, ln.last_subtitles_end = ln.seg + 1, None, 0, 0, 0
             ln.final_issued = False
         clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
+        if handle.eq is not None:
+            clip.eq = handle.eq
         if handle.level is not None:
             _with_level(clip, handle.level)
         if handle.limit is not None:

@@ -669,6 +669,44 @@ int gsv_eq(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, co
 int gsv_eq_host(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, const gsv_eq_design* designs, int n_designs,
                 float* out, gsv_eq_record* records, void* work, size_t work_bytes);
 
+/* Stream equaliser: the equaliser above for a stream that arrives in pushes (csrc/eqstream.h).  An equaliser is
+ * causal: a push of n samples emits n samples (no delay), a flush emits nothing extra (no ring-out) and returns the state to
+ * fresh, so that the next push starts a new stream with the same design.  The emitted samples, concatenated, are the bytes
+ * gsv_eq / gsv_eq_host return for the same finite samples as one clip with the same design, however the stream was cut into
+ * pushes: the stream runs the clip kernels' operations on 16384-sample chunks aligned to the stream index, and a chunk a push
+ * leaves unfinished is redone from its start state over its kept input.  A sample that is not finite enters the filter as 0.0
+ * and is copied to the output bit for bit (GSV_EQS_NONFINITE on the push, GSV_EQS_NONFINITE_EVER on the stream); it is kept out
+ * of the peaks, and every other output equals the stream with that sample replaced by 0.0.  Nothing clamps y.
+ *   state: caller-owned, gsv_eqstream_state_bytes() bytes, 16-byte aligned, made by gsv_eqstream_init from one design (HOST
+ *   memory in both entries): a header, the open chunk's joint start state, the coefficients and the scan's matrices, the open
+ *   chunk's input so far in two copies used in turn, and the per-push scratch of the chunk states.
+ *   gsv_eqstream_push: chunk fp32 [n_cap], n_cap 0..2^20 (chunk and out may be NULL at 0); n_dev NULL or a device int32 holding
+ *   the real length (clamped to 0..n_cap), e.g. gsv_stream_emit's record; out fp32 [n_cap], which may be chunk (in place): the
+ *   first `emitted` are written, nothing behind them; rec (device, 8-byte aligned).  Four launches whatever the length (two at
+ *   n_cap 0), nothing allocated, nothing read by the host.  A state gsv_eqstream_init did not make is not read through: flags
+ *   -1, out not written.
+ *   gsv_eqstream_init_host / gsv_eqstream_push_host: the same over HOST memory from the same scalar routines -- the CPU path
+ *   and the device's oracle (device samples and records equal the host's bit for bit); they need no GPU.
+ * GSV_ERR_ARG: a null pointer, a size that is negative or above 2^20, a design gsv_eq would refuse, a state that is too small or
+ * misaligned, a misaligned record. */
+typedef struct {
+    int32_t emitted;            /* samples this push wrote to out: its address serves as the next stage's n_dev */
+    int32_t flags;
+    float peak_in, peak_out;    /* max |x|, max |y| over the finite samples of this push (0: none) */
+    float peak_in_run, peak_out_run;    /* ... of the stream so far */
+    int64_t total;              /* samples of the stream so far (a flush reports the stream's length) */
+} gsv_eqstream_record;
+#define GSV_EQS_EQUALISED 1         /* the record of a state gsv_eqstream_init made */
+#define GSV_EQS_NONFINITE_EVER 2    /* a NaN or an infinity among the stream's samples so far */
+#define GSV_EQS_NONFINITE 4         /* ... among this push's samples */
+size_t gsv_eqstream_state_bytes(void);
+int gsv_eqstream_init(void* state, size_t bytes, const gsv_eq_design* design, void* stream);
+int gsv_eqstream_push(void* state, const float* chunk, int n_cap, const int32_t* n_dev, int flush, float* out,
+                      gsv_eqstream_record* rec, void* stream);
+int gsv_eqstream_init_host(void* state, size_t bytes, const gsv_eq_design* design);
+int gsv_eqstream_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
+                           gsv_eqstream_record* rec);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
