@@ -7,6 +7,8 @@
 // and for the stand-alone checker tools/eq_host_check.cpp.  Every multiply-add is an explicit fma and every order is fixed, so
 // contraction has nothing to change and device samples and records equal the host's bit for bit.  The device takes no sin, cos
 // or pow: the caller hands in normalised coefficients, and the powers of the state matrices are built on the host (eq_design).
+// The stream form (eqstream.h) owes the clip's bytes, so the sections of a span and the chain of the chunks are each one
+// function on the device (eq_sections, eq_chain_walk) and one on the host (eq_sections_host, eq_chain_host) that both forms call.
 //
 // The scan, section after section.  A block of EQ_T threads takes a span of EQ_T * EQ_R samples; thread t holds its EQ_R
 // consecutive samples in fp64 registers.  For section s = 0, 1, ...: the thread runs its samples from zero state (thread 0:
@@ -224,10 +226,43 @@ inline void eq_design(const EqCoefs& d, EqDesign* out) {
     for (int i = 0; i < EQ_NS * EQ_NS; ++i) D.J[i] = (double)A[i];
 }
 
+// the sections of one span as the block's threads run them (eq_sections below), over the runs v[0 .. nt - 1] from the joint
+// state `carry`: v becomes the last section's output and carry the state behind run nt - 1.  ends: the end state alone -- the
+// last section's rerun is left out and v is then not its output.
+inline void eq_sections_host(const EqDesign& D, int nt, bool ends, double (*v)[EQ_R], EqState& carry) {
+    static thread_local double st[2][EQ_T], nx[2][EQ_T];
+    for (int s = 0; s < D.ns; ++s) {
+        const double* b = D.b[s];
+        const double* na = D.na[s];
+        const double c0 = carry.s[2 * s], c1 = carry.s[2 * s + 1];
+        for (int t = 0; t < nt; ++t) {
+            double z0 = t == 0 ? c0 : 0.0, z1 = t == 0 ? c1 : 0.0;
+            for (int i = 0; i < EQ_R; ++i) eq_step(b, na, z0, z1, v[t][i]);
+            st[0][t] = z0; st[1][t] = z1;
+        }
+        for (int k = 0; k < EQ_LOG_T; ++k) {
+            const int d = 1 << k;
+            for (int t = 0; t < nt; ++t) {
+                double e0 = st[0][t], e1 = st[1][t];
+                if (t >= d) eq_combine(D.P[s][k], st[0][t - d], st[1][t - d], e0, e1);
+                nx[0][t] = e0; nx[1][t] = e1;
+            }
+            memcpy(st, nx, sizeof st);
+        }
+        carry.s[2 * s] = st[0][nt - 1];
+        carry.s[2 * s + 1] = st[1][nt - 1];
+        if (ends && s == D.ns - 1) break;
+        for (int t = 0; t < nt; ++t) {
+            double z0 = t == 0 ? c0 : st[0][t - 1], z1 = t == 0 ? c1 : st[1][t - 1];
+            for (int i = 0; i < EQ_R; ++i) v[t][i] = eq_step(b, na, z0, z1, v[t][i]);
+        }
+    }
+}
+
 // the samples [lo, hi) of a clip span by span from the joint state `carry`, as one block walks them -> the state behind them.
 // y null: the first half only (the end states of the chunks); else y and both peaks' bits too
 inline EqState eq_chunk_host(const float* x, int lo, int hi, const EqDesign& D, EqState carry, float* y, uint32_t* peak_in, uint32_t* peak_out) {
-    static thread_local double v[EQ_T][EQ_R], st[2][EQ_T], nx[2][EQ_T];
+    static thread_local double v[EQ_T][EQ_R];
     for (int s0 = lo; s0 < hi; s0 += EQ_SPAN) {
         const int cnt = hi - s0 < EQ_SPAN ? hi - s0 : EQ_SPAN;
         for (int k = 0; k < EQ_SPAN; ++k) {
@@ -239,32 +274,7 @@ inline EqState eq_chunk_host(const float* x, int lo, int hi, const EqDesign& D, 
             }
             v[k / EQ_R][k % EQ_R] = (double)xv;
         }
-        for (int s = 0; s < D.ns; ++s) {
-            const double* b = D.b[s];
-            const double* na = D.na[s];
-            const double c0 = carry.s[2 * s], c1 = carry.s[2 * s + 1];
-            for (int t = 0; t < EQ_T; ++t) {
-                double z0 = t == 0 ? c0 : 0.0, z1 = t == 0 ? c1 : 0.0;
-                for (int i = 0; i < EQ_R; ++i) eq_step(b, na, z0, z1, v[t][i]);
-                st[0][t] = z0; st[1][t] = z1;
-            }
-            for (int k = 0; k < EQ_LOG_T; ++k) {
-                const int d = 1 << k;
-                for (int t = 0; t < EQ_T; ++t) {
-                    double e0 = st[0][t], e1 = st[1][t];
-                    if (t >= d) eq_combine(D.P[s][k], st[0][t - d], st[1][t - d], e0, e1);
-                    nx[0][t] = e0; nx[1][t] = e1;
-                }
-                memcpy(st, nx, sizeof st);
-            }
-            carry.s[2 * s] = st[0][EQ_T - 1];
-            carry.s[2 * s + 1] = st[1][EQ_T - 1];
-            if (!y && s == D.ns - 1) break;
-            for (int t = 0; t < EQ_T; ++t) {
-                double z0 = t == 0 ? c0 : st[0][t - 1], z1 = t == 0 ? c1 : st[1][t - 1];
-                for (int i = 0; i < EQ_R; ++i) v[t][i] = eq_step(b, na, z0, z1, v[t][i]);
-            }
-        }
+        eq_sections_host(D, EQ_T, !y, v, carry);
         for (int k = 0; y && k < cnt; ++k) {
             const float o = loud_store(v[k / EQ_R][k % EQ_R]);
             const uint32_t a = loud_abs_bits(o);
@@ -275,18 +285,14 @@ inline EqState eq_chunk_host(const float* x, int lo, int hi, const EqDesign& D, 
     return carry;
 }
 
-// the true start state of every chunk of a clip from the chunks' end states: what the chain wave does
-inline void eq_chain_host(const EqDesign& D, int nch, const EqState* ends, EqState* starts) {
-    EqState s;
-    memset(&s, 0, sizeof s);
-    for (int c = 0; c < nch; ++c) {
-        starts[c] = s;
-        if (c + 1 < nch) {
-            EqState nxt;
-            for (int i = 0; i < EQ_NS; ++i) nxt.s[i] = eq_chain_row(D.J + EQ_NS * i, s.s, ends[c].s[i]);
-            s = nxt;
-        }
-    }
+// what the chain wave does (eq_chain_walk below): from the start state `first` of a chunk over `links` chunks with their end
+// states from zero state -> starts[0 .. links], the true start state of each and of the chunk behind them.  links < 0 (a clip
+// of no chunks): nothing written
+inline void eq_chain_host(const EqDesign& D, const EqState& first, int links, const EqState* ends, EqState* starts) {
+    if (links < 0) return;
+    starts[0] = first;
+    for (int c = 0; c < links; ++c)
+        for (int i = 0; i < EQ_NS; ++i) starts[c + 1].s[i] = eq_chain_row(D.J + EQ_NS * i, starts[c].s, ends[c].s[i]);
 }
 
 // the whole call over host memory.  work holds eq_layout's bytes; out may be x (in place).
@@ -313,7 +319,7 @@ inline void eq_run_host(const float* x, const EqClip* clips, int n_clips, const 
             ns = Dd.ns;
             for (int k = 0; k + 1 < r.nch; ++k)
                 ends[r.soff + k] = eq_chunk_host(xc, k * EQ_CHUNK, (k + 1) * EQ_CHUNK, Dd, zero, nullptr, nullptr, nullptr);
-            eq_chain_host(Dd, r.nch, ends + r.soff, starts + r.soff);
+            eq_chain_host(Dd, zero, r.nch - 1, ends + r.soff, starts + r.soff);
             for (int k = 0; k < r.nch; ++k) {
                 const long long hi = (long long)(k + 1) * EQ_CHUNK;
                 eq_chunk_host(xc, k * EQ_CHUNK, hi < r.n ? (int)hi : r.n, Dd, starts[r.soff + k], yws + r.yoff, &pin, &pout);
@@ -338,11 +344,83 @@ inline void eq_run_host(const float* x, const EqClip* clips, int n_clips, const 
 // ------------------------------------------------------------------------------------------------------------------
 // the device kernels
 // ------------------------------------------------------------------------------------------------------------------
+// The sections of one span: the one text of eq_filter_kernel and of eqs_filter_kernel (eqstream.h).  Thread tid's run is staged
+// at `mine` (EQ_R floats of LDS); v becomes the last section's output for the run and carry_s (EQ_NS doubles of LDS) goes from
+// the joint state in front of the span to the state behind it.  ENDS: the end state alone -- the last section's rerun is left
+// out, and v is then not its output.  The scan's exchange sc is double-buffered: one barrier per step.  The section loop is not
+// unrolled and indexes no register array (the carried states live in LDS), so the section count costs neither registers nor
+// scratch.
+// Barriers: entered by all EQ_T threads of the block (ns is block-uniform, and so is the ENDS exit) behind a barrier that
+// follows the staging of the runs, the last write of carry_s and the last span's reads of sc.  It returns without one: the
+// caller owes a barrier before carry_s is read, sc or carry_s is written again, or a run is read by another thread.
+template <bool ENDS>
+__device__ __forceinline__ void eq_sections(const EqDesign* __restrict__ D, int ns, const float* mine, double (*sc)[2][EQ_T], double* carry_s,
+                                            double (&v)[EQ_R]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < EQ_R; ++i) v[i] = (double)mine[i];
+#pragma unroll 1
+    for (int s = 0; s < ns; ++s) {
+        const double b[3] = {D->b[s][0], D->b[s][1], D->b[s][2]};
+        const double na[2] = {D->na[s][0], D->na[s][1]};
+        double c0 = 0.0, c1 = 0.0;
+        if (tid == 0) { c0 = carry_s[2 * s]; c1 = carry_s[2 * s + 1]; }
+        double e0 = c0, e1 = c1;
+#pragma unroll
+        for (int i = 0; i < EQ_R; ++i) eq_step(b, na, e0, e1, v[i]);
+#pragma unroll 1
+        for (int k = 0; k < EQ_LOG_T; ++k) {
+            const int d = 1 << k, buf = k & 1;
+            sc[buf][0][tid] = e0;
+            sc[buf][1][tid] = e1;
+            __syncthreads();
+            if (tid >= d) {
+                const double P[4] = {D->P[s][k][0], D->P[s][k][1], D->P[s][k][2], D->P[s][k][3]};
+                eq_combine(P, sc[buf][0][tid - d], sc[buf][1][tid - d], e0, e1);
+            }
+        }
+        sc[EQ_LOG_T & 1][0][tid] = e0;
+        sc[EQ_LOG_T & 1][1][tid] = e1;
+        if (tid == EQ_T - 1) { carry_s[2 * s] = e0; carry_s[2 * s + 1] = e1; }      // thread 0 read its carry before the scan
+        if (ENDS && s == ns - 1) break;
+        __syncthreads();
+        if (tid > 0) { c0 = sc[EQ_LOG_T & 1][0][tid - 1]; c1 = sc[EQ_LOG_T & 1][1][tid - 1]; }
+#pragma unroll
+        for (int i = 0; i < EQ_R; ++i) v[i] = eq_step(b, na, c0, c1, v[i]);
+    }
+}
+
+// The chain of one wave, the one text of eq_chain_kernel and of eqs_chain_kernel (eqstream.h): lane i keeps row i of J and
+// element i (`mine`) of the joint start state of a chunk, and walks `links` chunks with their end states from zero state:
+// starts[0 .. links] are written, ends[0 .. links - 1] read; links < 0: nothing.  Entered by all EQ_LANES lanes with one
+// `links`; two barriers per link.
+__device__ __forceinline__ void eq_chain_walk(const double* __restrict__ J, double mine, int links, const EqState* __restrict__ ends,
+                                              EqState* __restrict__ starts) {
+    __shared__ double s[EQ_NS];
+    const int lane = threadIdx.x;
+    const bool on = lane < EQ_NS;
+    double Jrow[EQ_NS];
+#pragma unroll
+    for (int j = 0; j < EQ_NS; ++j) Jrow[j] = on ? J[EQ_NS * lane + j] : 0.0;
+    for (int c = 0; c <= links; ++c) {
+        if (on) {
+            starts[c].s[lane] = mine;
+            s[lane] = mine;
+        }
+        if (c == links) break;
+        __syncthreads();
+        double left[EQ_NS];
+#pragma unroll
+        for (int j = 0; j < EQ_NS; ++j) left[j] = s[j];
+        if (on) mine = eq_chain_row(Jrow, left, ends[c].s[lane]);
+        __syncthreads();
+    }
+}
+
 // One block per chunk of a clip.  ENDS: the first half over the chunks that have a successor -- from zero state to the chunk's
 // end state, nothing else written.  Else the full pass from the chunk's true start state: y and both peaks.  The span is staged in
 // LDS by coalesced loads, each thread's run padded by one float so the runs start in different banks; y goes back through the
-// same slots.  The scan's exchange is double-buffered: one barrier per step.  The section loop is not unrolled and indexes no
-// register array (the carried states live in LDS), so the section count costs neither registers nor scratch.
+// same slots.
 template <bool ENDS>
 static __global__ __launch_bounds__(EQ_T) void eq_filter_kernel(const float* __restrict__ x, const EqRow* __restrict__ rows,
                                                                 const EqDesign* __restrict__ designs, float* __restrict__ yws,
@@ -395,37 +473,7 @@ static __global__ __launch_bounds__(EQ_T) void eq_filter_kernel(const float* __r
         }
         __syncthreads();                // xs, and carry_s of the last span (or of the prologue)
         double v[EQ_R];
-#pragma unroll
-        for (int i = 0; i < EQ_R; ++i) v[i] = (double)mine[i];
-#pragma unroll 1
-        for (int s = 0; s < ns; ++s) {
-            const double b[3] = {D->b[s][0], D->b[s][1], D->b[s][2]};
-            const double na[2] = {D->na[s][0], D->na[s][1]};
-            double c0 = 0.0, c1 = 0.0;
-            if (tid == 0) { c0 = carry_s[2 * s]; c1 = carry_s[2 * s + 1]; }
-            double e0 = c0, e1 = c1;
-#pragma unroll
-            for (int i = 0; i < EQ_R; ++i) eq_step(b, na, e0, e1, v[i]);
-#pragma unroll 1
-            for (int k = 0; k < EQ_LOG_T; ++k) {
-                const int d = 1 << k, buf = k & 1;
-                sc[buf][0][tid] = e0;
-                sc[buf][1][tid] = e1;
-                __syncthreads();
-                if (tid >= d) {
-                    const double P[4] = {D->P[s][k][0], D->P[s][k][1], D->P[s][k][2], D->P[s][k][3]};
-                    eq_combine(P, sc[buf][0][tid - d], sc[buf][1][tid - d], e0, e1);
-                }
-            }
-            sc[EQ_LOG_T & 1][0][tid] = e0;
-            sc[EQ_LOG_T & 1][1][tid] = e1;
-            if (tid == EQ_T - 1) { carry_s[2 * s] = e0; carry_s[2 * s + 1] = e1; }      // thread 0 read its carry before the scan
-            if (ENDS && s == ns - 1) break;
-            __syncthreads();
-            if (tid > 0) { c0 = sc[EQ_LOG_T & 1][0][tid - 1]; c1 = sc[EQ_LOG_T & 1][1][tid - 1]; }
-#pragma unroll
-            for (int i = 0; i < EQ_R; ++i) v[i] = eq_step(b, na, c0, c1, v[i]);
-        }
+        eq_sections<ENDS>(D, ns, mine, sc, carry_s, v);
         if (!ENDS) {
             if (tid * EQ_R < cnt) {
 #pragma unroll
@@ -453,33 +501,14 @@ static __global__ __launch_bounds__(EQ_T) void eq_filter_kernel(const float* __r
     if (tid < 2) atomicMax(&peaks[2 * blockIdx.y + tid], peak_s[tid]);      // integer maxima: the order of the chunks does not show
 }
 
-// between the two: one wave per clip chains its chunks (lane i keeps row i of J) and clears the clip's peaks
+// between the two: one wave per clip chains its chunks from zero state and clears the clip's peaks
 static __global__ __launch_bounds__(EQ_LANES) void eq_chain_kernel(const EqRow* __restrict__ rows, const EqDesign* __restrict__ designs,
                                                                    const EqState* __restrict__ ends, EqState* __restrict__ starts,
                                                                    uint32_t* __restrict__ peaks) {
-    __shared__ double s[EQ_NS];
     const EqRow row = rows[blockIdx.x];
-    const int lane = threadIdx.x;
-    if (lane < 2) peaks[2 * blockIdx.x + lane] = 0;
+    if (threadIdx.x < 2) peaks[2 * blockIdx.x + threadIdx.x] = 0;
     if (row.design < 0) return;                 // block-uniform
-    const bool on = lane < EQ_NS;
-    double Jrow[EQ_NS];
-#pragma unroll
-    for (int j = 0; j < EQ_NS; ++j) Jrow[j] = on ? designs[row.design].J[EQ_NS * lane + j] : 0.0;
-    double mine = 0.0;
-    for (int c = 0; c < row.nch; ++c) {
-        if (on) {
-            starts[row.soff + c].s[lane] = mine;
-            s[lane] = mine;
-        }
-        if (c + 1 == row.nch) break;
-        __syncthreads();
-        double left[EQ_NS];
-#pragma unroll
-        for (int j = 0; j < EQ_NS; ++j) left[j] = s[j];
-        if (on) mine = eq_chain_row(Jrow, left, ends[row.soff + c].s[lane]);
-        __syncthreads();
-    }
+    eq_chain_walk(designs[row.design].J, 0.0, row.nch - 1, ends + row.soff, starts + row.soff);
 }
 
 // last: the record, and out = y (a clip that was equalised) or x (measure only, or a NaN or an infinity among the samples: in

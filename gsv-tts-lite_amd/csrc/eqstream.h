@@ -9,15 +9,18 @@
 // the state keeps the joint start state S_k of the open chunk and the open chunk's input so far, a push reruns the open chunk's
 // full pass from S_k over the kept samples and the new ones and writes the outputs that were not emitted before, and for every
 // chunk the push completes it runs the pass from zero state, chains with J, and runs the chunks behind it: the clip's three
-// launches.  Nothing is continued by a recurrence of its own.
+// launches.  Nothing is continued by a recurrence of its own, and the operations are the same because they are the same text:
+// the sections of a span are eq.h's eq_sections (eq_sections_host in the twin) and the chain is its eq_chain_walk
+// (eq_chain_host), called from here as from the clip's kernels.  What is the stream's own is where a sample comes from and
+// which outputs are written.
 //
 // A sample that is not finite.  A clip holding one comes back unchanged, which a stream cannot know ahead of time; here such a
 // sample enters the filter as 0.0 and is copied to the output bit for bit, so the state is never poisoned and every other output
 // equals the stream with that sample replaced by 0.0 (cut-independent too).  The push's record says EQS_NONFINITE, the stream's
 // EQS_NONFINITE_EVER, and such samples are kept out of both peaks.
 //
-// eq_step, eq_combine, eq_chain_row, eq_design and loud_store are eq.h's; what is new here -- the plan of a push, the sample as it
-// enters the filter, the record -- is one __host__ __device__ text for the kernels, for the host twin eqs_push_host
+// eq_design and loud_store are used as eq.h uses them; what is new here -- the plan of a push, the sample as it enters the filter, the
+// record -- is one __host__ __device__ text for the kernels, for the host twin eqs_push_host
 // (gsv_eqstream_push_host: the CPU path and the device's oracle) and for tools/eqstream_host_check.cpp.
 //
 // The caller-owned state, every part 16-byte aligned:
@@ -39,6 +42,7 @@ constexpr int EQS_MAX_BLOCKS = EQS_MAX_PUSH / EQ_CHUNK + 1;     // chunks one pu
 constexpr int EQS_LANES = 64;                       // lanes of the chain and the commit wave
 constexpr int EQS_EQUALISED = 1, EQS_NONFINITE_EVER = 2, EQS_NONFINITE = 4;     // record flags
 static_assert(EQS_MAX_PUSH % EQ_CHUNK == 0, "blocks of a push");
+static_assert(EQS_LANES == EQ_LANES, "eq_chain_walk's wave");
 
 struct EqsHeader {
     long long n;                            // samples of the stream so far (since the last flush)
@@ -59,13 +63,12 @@ struct EqsRecord {              // gsv_eqstream_record
 };
 static_assert(sizeof(EqsRecord) == 32, "record");
 
-LOUD_HD size_t eqs_a16(size_t v) { return (v + 15) & ~(size_t)15; }
 LOUD_HD size_t eqs_s_off() { return sizeof(EqsHeader); }
-LOUD_HD size_t eqs_design_off() { return eqs_s_off() + eqs_a16(sizeof(EqState)); }
-LOUD_HD size_t eqs_stash_off() { return eqs_design_off() + eqs_a16(sizeof(EqDesign)); }
+LOUD_HD size_t eqs_design_off() { return eqs_s_off() + loud_align16(sizeof(EqState)); }
+LOUD_HD size_t eqs_stash_off() { return eqs_design_off() + loud_align16(sizeof(EqDesign)); }
 LOUD_HD size_t eqs_ends_off() { return eqs_stash_off() + 2 * (size_t)EQ_CHUNK * sizeof(float); }
-LOUD_HD size_t eqs_starts_off() { return eqs_ends_off() + eqs_a16((size_t)EQS_MAX_BLOCKS * sizeof(EqState)); }
-LOUD_HD size_t eqs_state_bytes() { return eqs_starts_off() + eqs_a16((size_t)(EQS_MAX_BLOCKS + 1) * sizeof(EqState)); }
+LOUD_HD size_t eqs_starts_off() { return eqs_ends_off() + loud_align16((size_t)EQS_MAX_BLOCKS * sizeof(EqState)); }
+LOUD_HD size_t eqs_state_bytes() { return eqs_starts_off() + loud_align16((size_t)(EQS_MAX_BLOCKS + 1) * sizeof(EqState)); }
 
 struct EqsPlan {
     long long N0, N1;           // samples of the stream before and after this push
@@ -138,7 +141,7 @@ inline void eqs_init_host(unsigned char* state, const EqCoefs& d) {
 // of the samples at or behind N0, both peaks' bits, the flags, and with stash_new the chunk's input as it came
 inline EqState eqs_chunk_host(const float* stash_old, const float* chunk, long long N0, long long lo, long long hi, const EqDesign& D, EqState carry,
                               bool ends, float* out, float* stash_new, uint32_t* peak_in, uint32_t* peak_out, int32_t* flags) {
-    static thread_local double v[EQ_T][EQ_R], st[2][EQ_T], nx[2][EQ_T];
+    static thread_local double v[EQ_T][EQ_R];
     for (long long s0 = lo; s0 < hi; s0 += EQ_SPAN) {
         const int cnt = hi - s0 < EQ_SPAN ? (int)(hi - s0) : EQ_SPAN;
         // a prefix of the scan reads the runs to its left alone, and the state behind a span the push leaves short is not used:
@@ -159,32 +162,7 @@ inline EqState eqs_chunk_host(const float* stash_old, const float* chunk, long l
             }
             v[k / EQ_R][k % EQ_R] = (double)xv;
         }
-        for (int s = 0; s < D.ns; ++s) {
-            const double* b = D.b[s];
-            const double* na = D.na[s];
-            const double c0 = carry.s[2 * s], c1 = carry.s[2 * s + 1];
-            for (int t = 0; t < nt; ++t) {
-                double z0 = t == 0 ? c0 : 0.0, z1 = t == 0 ? c1 : 0.0;
-                for (int i = 0; i < EQ_R; ++i) eq_step(b, na, z0, z1, v[t][i]);
-                st[0][t] = z0; st[1][t] = z1;
-            }
-            for (int k = 0; k < EQ_LOG_T; ++k) {
-                const int d = 1 << k;
-                for (int t = 0; t < nt; ++t) {
-                    double e0 = st[0][t], e1 = st[1][t];
-                    if (t >= d) eq_combine(D.P[s][k], st[0][t - d], st[1][t - d], e0, e1);
-                    nx[0][t] = e0; nx[1][t] = e1;
-                }
-                memcpy(st, nx, sizeof st);
-            }
-            carry.s[2 * s] = st[0][nt - 1];
-            carry.s[2 * s + 1] = st[1][nt - 1];
-            if (ends && s == D.ns - 1) break;
-            for (int t = 0; t < nt; ++t) {
-                double z0 = t == 0 ? c0 : st[0][t - 1], z1 = t == 0 ? c1 : st[1][t - 1];
-                for (int i = 0; i < EQ_R; ++i) v[t][i] = eq_step(b, na, z0, z1, v[t][i]);
-            }
-        }
+        eq_sections_host(D, nt, ends, v, carry);
         for (int k = 0; !ends && k < cnt; ++k) {
             if (s0 + k < N0) continue;          // emitted by an earlier push
             const float raw = chunk[s0 + k - N0];       // out may be the chunk: read before the write
@@ -222,9 +200,7 @@ inline void eqs_push_host(unsigned char* state, const float* chunk, int n, bool 
         const long long lo = (pl.k0 + b) * EQ_CHUNK;
         ends[b] = eqs_chunk_host(stash_old, chunk, pl.N0, lo, lo + EQ_CHUNK, D, zero, true, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
-    starts[0] = *S;
-    for (int b = 0; b < pl.done; ++b)
-        for (int i = 0; i < EQ_NS; ++i) starts[b + 1].s[i] = eq_chain_row(D.J + EQ_NS * i, starts[b].s, ends[b].s[i]);
+    eq_chain_host(D, *S, pl.done, ends, starts);
     for (int b = 0; b < pl.nb; ++b) {
         const long long lo = (pl.k0 + b) * EQ_CHUNK;
         const bool open = lo + EQ_CHUNK > pl.N1;
@@ -245,7 +221,7 @@ __device__ __forceinline__ int eqs_len_dev(const int32_t* n_dev, int n_cap) { re
 // eq_filter_kernel for a push: one block per chunk of the stream that the push touches, block b on chunk k0 + b.  ENDS: over the
 // chunks the push completes, from zero state to the chunk's end state -> ends[b], nothing else written.  Else the full pass from
 // starts[b]: the outputs of the push's own samples, both peaks, the flags, and -- the block of the chunk left open -- the chunk's
-// input so far into the other stash.  The LDS staging, the padded runs and the double-buffered scan exchange are eq_filter_kernel's.
+// input so far into the other stash.  The padded runs in LDS are laid out as eq_filter_kernel's, and eq_sections runs over them.
 // chunk and out may be one buffer: a block reads a span (and stashes it) before it writes the span's outputs, and no block reads
 // another block's samples.
 template <bool ENDS>
@@ -298,37 +274,7 @@ static __global__ __launch_bounds__(EQ_T) void eqs_filter_kernel(unsigned char* 
         }
         __syncthreads();                // xs, and carry_s of the last span (or of the prologue)
         double v[EQ_R];
-#pragma unroll
-        for (int i = 0; i < EQ_R; ++i) v[i] = (double)mine[i];
-#pragma unroll 1
-        for (int s = 0; s < ns; ++s) {
-            const double b[3] = {D->b[s][0], D->b[s][1], D->b[s][2]};
-            const double na[2] = {D->na[s][0], D->na[s][1]};
-            double c0 = 0.0, c1 = 0.0;
-            if (tid == 0) { c0 = carry_s[2 * s]; c1 = carry_s[2 * s + 1]; }
-            double e0 = c0, e1 = c1;
-#pragma unroll
-            for (int i = 0; i < EQ_R; ++i) eq_step(b, na, e0, e1, v[i]);
-#pragma unroll 1
-            for (int k = 0; k < EQ_LOG_T; ++k) {
-                const int d = 1 << k, buf = k & 1;
-                sc[buf][0][tid] = e0;
-                sc[buf][1][tid] = e1;
-                __syncthreads();
-                if (tid >= d) {
-                    const double P[4] = {D->P[s][k][0], D->P[s][k][1], D->P[s][k][2], D->P[s][k][3]};
-                    eq_combine(P, sc[buf][0][tid - d], sc[buf][1][tid - d], e0, e1);
-                }
-            }
-            sc[EQ_LOG_T & 1][0][tid] = e0;
-            sc[EQ_LOG_T & 1][1][tid] = e1;
-            if (tid == EQ_T - 1) { carry_s[2 * s] = e0; carry_s[2 * s + 1] = e1; }      // thread 0 read its carry before the scan
-            if (ENDS && s == ns - 1) break;
-            __syncthreads();
-            if (tid > 0) { c0 = sc[EQ_LOG_T & 1][0][tid - 1]; c1 = sc[EQ_LOG_T & 1][1][tid - 1]; }
-#pragma unroll
-            for (int i = 0; i < EQ_R; ++i) v[i] = eq_step(b, na, c0, c1, v[i]);
-        }
+        eq_sections<ENDS>(D, ns, mine, sc, carry_s, v);
         if (!ENDS) {
             if (tid * EQ_R < cnt) {
 #pragma unroll
@@ -371,36 +317,16 @@ static __global__ __launch_bounds__(EQ_T) void eqs_filter_kernel(unsigned char* 
     }
 }
 
-// between the two: one wave chains the chunks the push completes (lane i keeps row i of J) -> the start state of every chunk the
-// push touches, starts[0] the state's S
+// between the two: one wave chains the chunks the push completes from the state's S (eq_chain_walk) -> the start state of every
+// chunk the push touches
 static __global__ __launch_bounds__(EQS_LANES) void eqs_chain_kernel(unsigned char* state, int n_cap, const int32_t* n_dev) {
-    __shared__ double s[EQ_NS];
     const EqsHeader h = *reinterpret_cast<const EqsHeader*>(state);
     if (h.magic != EQS_MAGIC) return;
     const EqsPlan pl = eqs_plan(h.n, eqs_len_dev(n_dev, n_cap));
-    const EqDesign* __restrict__ D = reinterpret_cast<const EqDesign*>(state + eqs_design_off());
-    const EqState* __restrict__ ends = reinterpret_cast<const EqState*>(state + eqs_ends_off());
-    EqState* __restrict__ starts = reinterpret_cast<EqState*>(state + eqs_starts_off());
     const int lane = threadIdx.x;
-    const int done = pl.done < EQS_MAX_BLOCKS ? pl.done : EQS_MAX_BLOCKS;
-    const bool on = lane < EQ_NS;
-    double Jrow[EQ_NS];
-#pragma unroll
-    for (int j = 0; j < EQ_NS; ++j) Jrow[j] = on ? D->J[EQ_NS * lane + j] : 0.0;
-    double mine = on ? reinterpret_cast<const EqState*>(state + eqs_s_off())->s[lane] : 0.0;
-    for (int c = 0; c <= done; ++c) {
-        if (on) {
-            starts[c].s[lane] = mine;
-            s[lane] = mine;
-        }
-        if (c == done) break;
-        __syncthreads();
-        double left[EQ_NS];
-#pragma unroll
-        for (int j = 0; j < EQ_NS; ++j) left[j] = s[j];
-        if (on) mine = eq_chain_row(Jrow, left, ends[c].s[lane]);
-        __syncthreads();
-    }
+    const double mine = lane < EQ_NS ? reinterpret_cast<const EqState*>(state + eqs_s_off())->s[lane] : 0.0;
+    eq_chain_walk(reinterpret_cast<const EqDesign*>(state + eqs_design_off())->J, mine, pl.done < EQS_MAX_BLOCKS ? pl.done : EQS_MAX_BLOCKS,
+                  reinterpret_cast<const EqState*>(state + eqs_ends_off()), reinterpret_cast<EqState*>(state + eqs_starts_off()));
 }
 
 // last, one wave: the record, S of the chunk now open, the header.  Every lane has read the header before the barrier; one

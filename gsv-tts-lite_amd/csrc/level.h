@@ -71,12 +71,11 @@ struct LevelHeader {
 static_assert(sizeof(LevelHeader) == 2864 && sizeof(LevelHeader) % 16 == 0 && offsetof(LevelHeader, K) == 52, "state header (level.py reads K and the knots)");
 
 LOUD_HD size_t level_knots_off() { return sizeof(LevelHeader); }
-LOUD_HD size_t level_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-LOUD_HD size_t level_sums_off(int cap_hops) { return level_knots_off() + level_align16((size_t)(cap_hops + 2) * sizeof(double)); }
-LOUD_HD size_t level_blocks_off(int cap_hops) { return level_sums_off(cap_hops) + level_align16((size_t)cap_hops * sizeof(double)); }
-LOUD_HD size_t level_ring_off(int cap_hops, int cap_blocks) { return level_blocks_off(cap_hops) + level_align16((size_t)cap_blocks * sizeof(double)); }
+LOUD_HD size_t level_sums_off(int cap_hops) { return level_knots_off() + loud_align16((size_t)(cap_hops + 2) * sizeof(double)); }
+LOUD_HD size_t level_blocks_off(int cap_hops) { return level_sums_off(cap_hops) + loud_align16((size_t)cap_hops * sizeof(double)); }
+LOUD_HD size_t level_ring_off(int cap_hops, int cap_blocks) { return level_blocks_off(cap_hops) + loud_align16((size_t)cap_blocks * sizeof(double)); }
 LOUD_HD size_t level_state_bytes(int cap_hops, int cap_blocks, int ring) {
-    return level_ring_off(cap_hops, cap_blocks) + level_align16((size_t)ring * sizeof(float));
+    return level_ring_off(cap_hops, cap_blocks) + loud_align16((size_t)ring * sizeof(float));
 }
 
 // knot h of the grid: the lower bound of loud_block_bounds, every expression in fp64 in this order

@@ -184,11 +184,12 @@ LOUD_HD LoudRecord loud_finish(const LoudRow& row, const LoudParams& p, uint32_t
     return r;
 }
 
+// the parts of every workspace and caller-owned state here (level.h, eq.h, eqstream.h too) start 16-byte aligned
+LOUD_HD size_t loud_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
 // ------------------------------------------------------------------------------------------------------------------
 // host only: the constants, the workspace layout, the serial twin
 // ------------------------------------------------------------------------------------------------------------------
-inline size_t loud_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct LoudLayout {
     size_t rows_off, y_off, z_off, ends_off, starts_off, peak_off, bytes;
     long long y_total, z_total, s_total;
