@@ -44,6 +44,7 @@ EXPORTS = [
     "gsv_limstream_push_host",
     "gsv_eq_work_bytes", "gsv_eq", "gsv_eq_host",
     "gsv_eqstream_state_bytes", "gsv_eqstream_init", "gsv_eqstream_push", "gsv_eqstream_init_host", "gsv_eqstream_push_host",
+    "gsv_compressor_work_bytes", "gsv_compressor", "gsv_compressor_host", "gsv_compressor_math_host",
 ]
 
 
@@ -219,6 +220,26 @@ class EqstreamRecord(ctypes.Structure):
 EQS_EQUALISED, EQS_NONFINITE_EVER, EQS_NONFINITE = 1, 2, 4      # GSV_EQS_*
 EQS_MAX_CHUNK = 1 << 20                 # csrc/eqstream.h: samples of one push
 
+
+class CompressorClip(ctypes.Structure):
+    """gsv_compressor_clip: one clip of gsv_compressor; params -1: measure the peaks, copy"""
+    _fields_ = [("offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("params", ctypes.c_int32)]
+
+
+class CompressorParams(ctypes.Structure):
+    """gsv_compressor_params: the one-pole coefficients, the linear threshold, 1 / ratio - 1, the linear makeup"""
+    _fields_ = [("attack", ctypes.c_double), ("release", ctypes.c_double), ("threshold", ctypes.c_double), ("slope", ctypes.c_double),
+                ("makeup", ctypes.c_double)]
+
+
+class CompressorRecord(ctypes.Structure):
+    """gsv_compressor_record: what gsv_compressor found and did per clip"""
+    _fields_ = [("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float), ("min_gain", ctypes.c_float), ("flags", ctypes.c_int32)]
+
+
+CMP_COMPRESSED, CMP_NONFINITE = 1, 4    # GSV_CMP_*
+CMP_RUN, CMP_SPAN, CMP_CHUNK = 16, 512 * 16, 2 * 512 * 16       # csrc/compressor.h: CMP_R, CMP_SPAN, CMP_CHUNK
+
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
 
@@ -356,6 +377,9 @@ def lib():
         "gsv_eqstream_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_eqstream_init_host": [vp, sz, ctypes.POINTER(EqDesign)],
         "gsv_eqstream_push_host": [vp, vp, i, vp, i, vp, vp],
+        "gsv_compressor": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz, vp],
+        "gsv_compressor_host": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz],
+        "gsv_compressor_math_host": [i, vp, vp, sz],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -402,6 +426,8 @@ def lib():
     L.gsv_limiter_work_bytes.restype = sz
     L.gsv_eq_work_bytes.argtypes = [ctypes.POINTER(EqClip), i, ctypes.POINTER(EqDesign), i]
     L.gsv_eq_work_bytes.restype = sz
+    L.gsv_compressor_work_bytes.argtypes = [ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i]
+    L.gsv_compressor_work_bytes.restype = sz
     L.gsv_eqstream_state_bytes.argtypes = []
     L.gsv_eqstream_state_bytes.restype = sz
     L.gsv_limstream_state_bytes.argtypes = [i, i]

@@ -105,6 +105,8 @@ class AudioClip:
         self.gain_min = None        # far, and the smallest gain among this clip's samples; `limited`: the limiter has acted so far
         self.eq = None              # a clip made with eq= (or by equalised()): the eq.EqRecord -- peak_in, peak_out, sections;
                                     # a clip of a stream made with eq=: the eq.EqStreamRecord of its push
+        self.comp = None            # a clip made with compress= (or by compressed()): the compressor.CmpRecord -- peak_in, peak_out,
+                                    # min_gain, compressed
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -152,7 +154,7 @@ class AudioClip:
         from . import loudness
         audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq = self.eq
+        out.eq, out.comp = self.eq, self.comp
         return _with_loudness(out, rec)
 
     def equalised(self, eq="voice") -> "AudioClip":
@@ -163,7 +165,19 @@ class AudioClip:
             raise ValueError("eq: a preset name (%s) or an eq.EQ, not %r" % (", ".join(eqm.PRESETS), type(eq).__name__))
         audio, rec = eqm.equalise(self.audio_data, self.samplerate, eq)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq = rec
+        out.eq, out.comp = rec, self.comp
+        return out
+
+    def compressed(self, c="voice") -> "AudioClip":
+        """a new clip through the compressor `c` -- a compressor.Compressor or a preset name (compressor.py) --, same
+        subtitles and text; its `comp` is the compressor.CmpRecord: the peak before and after, the smallest gain and whether the
+        compressor acted; `eq` is kept"""
+        from . import compressor as cm
+        if not isinstance(c, (str, cm.Compressor)):
+            raise ValueError("compress: a preset name (%s) or a compressor.Compressor, not %r" % (", ".join(cm.PRESETS), type(c).__name__))
+        audio, rec = cm.compress(self.audio_data, self.samplerate, c)
+        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
+        out.eq, out.comp = self.eq, rec
         return out
 
     def true_peak(self) -> float:
@@ -178,7 +192,7 @@ class AudioClip:
         from . import limiter
         audio, rec = limiter.limit(self.audio_data, self.samplerate, ceiling_db)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.lufs, out.gain, out.eq = self.lufs, self.gain, self.eq
+        out.lufs, out.gain, out.eq, out.comp = self.lufs, self.gain, self.eq, self.comp
         return _with_true_peak(out, rec)
 
     def _save_wav(self, save_path):
@@ -194,9 +208,9 @@ def _with_loudness(clip, rec):
     return clip
 
 
-def _with_records(clip, rec, lim, eqr=None):
-    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr) or several of them"""
-    clip.eq = eqr
+def _with_records(clip, rec, lim, eqr=None, comp=None):
+    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr), compress= (comp) or several of them"""
+    clip.eq, clip.comp = eqr, comp
     if rec is not None:
         _with_loudness(clip, rec)
     return clip if lim is None else _with_true_peak(clip, lim)
@@ -218,6 +232,14 @@ def _check_eq(v, rate):
         return None
     from . import eq
     return eq.resolve(v, rate)
+
+
+def _check_compress(v):
+    """a compress= value: None, a preset name or a compressor.Compressor -> None (also for the identity) or the Compressor"""
+    if v is None:
+        return None
+    from . import compressor
+    return compressor.resolve(v)
 
 
 def _with_level(clip, rec):
@@ -897,11 +919,16 @@ class TTS:
     @torch.inference_mode()
     def infer(self, spk_audio_path, prompt_audio_path, prompt_audio_text, text, return_subtitles=False, top_k=15,
               top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-              sovits_model=None, loudness=None, true_peak=None, eq=None):
+              sovits_model=None, loudness=None, true_peak=None, eq=None, compress=None):
         """eq: None, a preset name ("voice": the three filters of the reference WebUI's enhance_audio) or an eq.EQ: the clip that
         would have been returned -- after the peak rule, trailing 0.2 s of zeros included -- goes through that equaliser on the
         device before the download (eq.py), ahead of loudness= and true_peak= as in the reference's chain; the clip
         then carries `eq`, the record with the peak before and after.  Nothing clamps that peak: true_peak= holds a ceiling.
+
+        compress: None, a preset name ("voice": -18 dB, 3.5 : 1, 1 ms / 100 ms, the compressor of enhance_audio) or a
+        compressor.Compressor: the clip goes through that compressor on the device (compressor.py) behind eq= and
+        ahead of loudness= and true_peak=, the reference's order; the clip then carries `comp`, the record with the peaks, the
+        smallest gain and whether the compressor acted.
 
         loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
         peak rule, trailing 0.2 s of zeros included -- is measured and scaled to it on the device before the download
@@ -912,6 +939,7 @@ class TTS:
         limited (the limiter acted).  With loudness= as well the gain to the target is applied whatever the peak becomes, and the
         limiter then holds the ceiling: the loudness that comes out is what the limiter leaves."""
         loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
+        compress = _check_compress(compress)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -947,10 +975,10 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
-                if loudness is not None or true_peak is not None or eq is not None:
-                    audio, rec, lim, eqr = self._finish_on_device(audio.float(), loudness, true_peak, eq)
+                if loudness is not None or true_peak is not None or eq is not None or compress is not None:
+                    audio, rec, lim, eqr, comp = self._finish_on_device(audio.float(), loudness, true_peak, eq, compress)
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text),
-                                         rec, lim, eqr)
+                                         rec, lim, eqr, comp)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -960,13 +988,15 @@ class TTS:
             finally:
                 self._empty_cache()
 
-    def _finish_on_device(self, audio, target, ceiling=None, eq=None):
-        """the tail of infer / infer_vc with eq=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1): dividing by
-        1 is exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then one gsv_eq
-        call (eq), one gsv_loudness call (target) and one gsv_limiter call (ceiling) over the finished clip in place, their records
-        written behind the samples: ONE download carries all -> (numpy samples, loudness record or None, limiter record or None,
-        eq record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
+    def _finish_on_device(self, audio, target, ceiling=None, eq=None, compress=None):
+        """the tail of infer / infer_vc with eq=, compress=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1):
+        dividing by 1 is exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then
+        one gsv_eq call (eq), one gsv_compressor call (compress), one gsv_loudness call (target) and one gsv_limiter call (ceiling)
+        over the finished clip in place -- the order of the reference's chain --, their records written behind the samples: ONE
+        download carries all -> (numpy samples, loudness record or None, limiter record or None, eq record or None, compressor
+        record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
         ceiling."""
+        from . import compressor as cm
         from . import eq as eqm
         from . import limiter as lm
         from . import loudness as ld
@@ -975,13 +1005,17 @@ class TTS:
         n = audio.numel() + int(0.2 * self.samplerate)
         words = (ld.RECORD_BYTES // 4 if target is not None else 0) + (lm.RECORD_BYTES // 4 if ceiling is not None else 0)
         eq_words = eqm.RECORD_BYTES // 4 if eq is not None else 0              # in front of the other two: 16 bytes keep their alignment
-        words += eq_words
+        cm_words = cm.RECORD_BYTES // 4 if compress is not None else 0         # and so do these 16
+        words += eq_words + cm_words
         tail = (n + 1) // 2 * 2 - audio.numel() + words                        # zeros to n, to an 8-byte boundary, the records
         buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
         at = buf.numel() - words
         if eq is not None:
             eqm.run_packed(buf[:n], [0], [n], [0], [eqm.design(eq, self.samplerate)], buf[:n], buf[at: at + eq_words].view(torch.uint8))
         eqr_at, at = at, at + eq_words
+        if compress is not None:
+            cm.run_packed(buf[:n], [0], [n], [0], [compress.coefficients(self.samplerate)], buf[:n], buf[at: at + cm_words].view(torch.uint8))
+        cmr_at, at = at, at + cm_words
         if target is not None:
             ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0 if ceiling is None else math.inf, buf[:n],
                           buf[at: at + ld.RECORD_BYTES // 4].view(torch.uint8))
@@ -992,16 +1026,18 @@ class TTS:
         rec = ld.records(host[at: at + ld.RECORD_BYTES // 4].view(np.uint8))[0] if target is not None else None
         lim = lm.records(host[host.size - lm.RECORD_BYTES // 4:].view(np.uint8))[0] if ceiling is not None else None
         eqr = eqm.records(host[eqr_at: eqr_at + eq_words].view(np.uint8))[0] if eq is not None else None
-        return host[:n], rec, lim, eqr
+        comp = cm.records(host[cmr_at: cmr_at + cm_words].view(np.uint8))[0] if compress is not None else None
+        return host[:n], rec, lim, eqr, comp
 
     @torch.inference_mode()
     def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
-                 loudness=None, true_peak=None, eq=None):
+                 loudness=None, true_peak=None, eq=None, compress=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
         decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
-        loudness, true_peak, eq: as in infer."""
+        loudness, true_peak, eq, compress: as in infer."""
         loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
-        finish = loudness is not None or true_peak is not None or eq is not None
+        compress = _check_compress(compress)
+        finish = loudness is not None or true_peak is not None or eq is not None or compress is not None
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -1019,7 +1055,7 @@ class TTS:
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
                 if finish:
-                    audio, rec, lim, eqr = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq)
+                    audio, rec, lim, eqr, comp = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq, compress)
                 else:
                     audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
@@ -1027,7 +1063,7 @@ class TTS:
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
                 if finish:
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
-                                                   prompt_audio_text), rec, lim, eqr)
+                                                   prompt_audio_text), rec, lim, eqr, comp)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1497,7 +1533,7 @@ class TTS:
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
-                      initial_suppression_steps=0, loudness=None, true_peak=None, eq=None):
+                      initial_suppression_steps=0, loudness=None, true_peak=None, eq=None, compress=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
 
@@ -1527,11 +1563,22 @@ class TTS:
         eq: None, a preset name or an eq.EQ for every text, or a list with one of those per TEXT (a wrong length raises
         ValueError; a bare list of eq.Band objects is not an equaliser: wrap it in eq.EQ).  The finished clips of the texts with
         one go through their equalisers in ONE packed gsv_eq call (eq.py) ahead of the loudness call, the distinct
-        designs passed once, and carry `eq`, as in infer.  A text with None comes back exactly as without the parameter."""
+        designs passed once, and carry `eq`, as in infer.  A text with None comes back exactly as without the parameter.
+
+        compress: None, a preset name or a compressor.Compressor for every text, or a list with one of those per TEXT (a wrong
+        length raises ValueError).  The finished clips of the texts with one go through their compressors in ONE packed
+        gsv_compressor call (compressor.py) behind the equaliser call and ahead of the loudness call, the distinct
+        parameter sets passed once, and carry `comp`, as in infer.  A text with None comes back exactly as without the parameter."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
+                if compress is not None:
+                    if isinstance(compress, (list, tuple)) and len(compress) != len(texts):
+                        raise ValueError("compress has %d entries for %d requests" % (len(compress), len(texts)))
+                    compress = [_check_compress(v) for v in (compress if isinstance(compress, (list, tuple)) else [compress] * len(texts))]
+                    if all(v is None for v in compress):
+                        compress = None
                 if loudness is not None:
                     loudness = [_check_loudness(v) for v in (slot_sampling.per_request("loudness", loudness, len(texts))
                                                              if slot_sampling.is_sequence(loudness) else [loudness] * len(texts))]
@@ -1737,6 +1784,13 @@ class TTS:
                     for i, a, rec in zip(pick, shaped, recs):
                         clips[i].audio_data = a
                         clips[i].eq = rec
+                if compress is not None:    # one packed call over the texts that asked, between the equaliser and the loudness call
+                    from . import compressor as cm
+                    pick = [i for i, v in enumerate(compress) if v is not None]
+                    shaped, recs = cm.compress([clips[i].audio_data for i in pick], self.samplerate, [compress[i] for i in pick], device=dev)
+                    for i, a, rec in zip(pick, shaped, recs):
+                        clips[i].audio_data = a
+                        clips[i].comp = rec
                 if loudness is not None:    # one packed call over the texts that asked
                     from . import loudness as ld
                     held = [true_peak is not None and true_peak[i] is not None for i in range(len(clips))]

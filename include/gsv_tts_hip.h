@@ -669,6 +669,55 @@ int gsv_eq(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, co
 int gsv_eq_host(const float* x, size_t n_x, const gsv_eq_clip* clips, int n_clips, const gsv_eq_design* designs, int n_designs,
                 float* out, gsv_eq_record* records, void* work, size_t work_bytes);
 
+/* Compressor: n_clips clips of one packed fp32 buffer, each through a feed-forward compressor with one of n_params parameter
+ * sets (csrc/compressor.h).  The level detector is the smooth decoupled peak detector (Giannoulis, Massberg, Reiss,
+ * JAES 2012), from zero state, in fp64, with a hard knee:
+ *   p = max(|x|, release p + (1 - release) |x|);  e = attack e + (1 - attack) p;
+ *   g = e <= threshold ? 1 : exp2(slope log2(e / threshold));  y = fp32(makeup g x), saturating at +-FLT_MAX.
+ *   params [n_params] (HOST memory in both entries): attack and release are the one-pole coefficients exp(-2 pi 1000 / (rate ms))
+ *   in (0, 1), threshold and makeup linear and positive, slope = 1 / ratio - 1 in [-1, 0].  Whoever makes them needs the sampling
+ *   rate; this call does not.
+ *   x: fp32 [n_x]; clip c is x[offset, offset + n_samples), mono; the clips do not overlap.  params: an index into params, or -1
+ *   for a clip whose peaks are measured and whose samples are copied.
+ *   out: x (in place) or a second buffer of n_x floats; only [offset, offset + n_samples) of each clip is written.
+ *   records [n_clips]: peak_in = max |x|, peak_out = max |y|, min_gain = the smallest g as fp32 (makeup excluded) and flags:
+ *   GSV_CMP_COMPRESSED when min_gain < 1.  A clip that never passes its threshold, with makeup 1, comes back bit for bit.  A clip
+ *   holding a NaN or an infinity (GSV_CMP_NONFINITE) comes back bit for bit, min_gain 1, peak_out = peak_in = that NaN or
+ *   infinity; so does a clip with params -1, flags 0.  An empty clip is legal.
+ *   work: caller-owned, gsv_compressor_work_bytes(clips, n_clips, params, n_params) bytes (0: bad arguments), 16-byte aligned.
+ *   gsv_compressor: x, out, records and work are DEVICE memory, clips and params HOST memory.  One small upload (the clip rows,
+ *   the parameters, the scans' powers) and at most six launches on `stream`; nothing allocated, nothing read back by the host.
+ *   gsv_compressor_host: the same over HOST memory from the same scalar routines -- the CPU path and the device's oracle (device
+ *   records and samples equal the host's bit for bit); it needs no GPU.
+ *   gsv_compressor_math_host: out[i] = the call's own log2 (which 0; positive normal arguments) or exp2 (which 1; the argument
+ *   clamped to [-1000, 1000]) of in[i], on the host: what the kernels evaluate, for whoever wants to measure it.
+ * GSV_ERR_ARG: a null pointer, a bad clip or parameter-set count (1..65535 clips, 0..65535 sets), an index outside the sets, a
+ * clip outside [0, n_x), a parameter outside the ranges above, a workspace that is too small or misaligned. */
+typedef struct {
+    int64_t offset;         /* first sample of the clip in x */
+    int32_t n_samples;
+    int32_t params;         /* index into params; -1: measure the peaks, copy */
+} gsv_compressor_clip;
+typedef struct {
+    double attack, release; /* one-pole coefficients, in (0, 1) */
+    double threshold;       /* linear, > 0 */
+    double slope;           /* 1 / ratio - 1, in [-1, 0] */
+    double makeup;          /* linear, > 0 */
+} gsv_compressor_params;
+typedef struct {
+    float peak_in, peak_out;
+    float min_gain;
+    int32_t flags;
+} gsv_compressor_record;
+#define GSV_CMP_COMPRESSED 1    /* the gain went below 1 somewhere in the clip */
+#define GSV_CMP_NONFINITE 4     /* a NaN or an infinity among the samples */
+size_t gsv_compressor_work_bytes(const gsv_compressor_clip* clips, int n_clips, const gsv_compressor_params* params, int n_params);
+int gsv_compressor(const float* x, size_t n_x, const gsv_compressor_clip* clips, int n_clips, const gsv_compressor_params* params,
+                   int n_params, float* out, gsv_compressor_record* records, void* work, size_t work_bytes, void* stream);
+int gsv_compressor_host(const float* x, size_t n_x, const gsv_compressor_clip* clips, int n_clips, const gsv_compressor_params* params,
+                        int n_params, float* out, gsv_compressor_record* records, void* work, size_t work_bytes);
+int gsv_compressor_math_host(int which, const double* in, double* out, size_t n);
+
 /* Stream equaliser: the equaliser above for a stream that arrives in pushes (csrc/eqstream.h).  An equaliser is
  * causal: a push of n samples emits n samples (no delay), a flush emits nothing extra (no ring-out) and returns the state to
  * fresh, so that the next push starts a new stream with the same design.  The emitted samples, concatenated, are the bytes
