@@ -45,6 +45,7 @@ EXPORTS = [
     "gsv_eq_work_bytes", "gsv_eq", "gsv_eq_host",
     "gsv_eqstream_state_bytes", "gsv_eqstream_init", "gsv_eqstream_push", "gsv_eqstream_init_host", "gsv_eqstream_push_host",
     "gsv_compressor_work_bytes", "gsv_compressor", "gsv_compressor_host", "gsv_compressor_math_host",
+    "gsv_cmpstream_state_bytes", "gsv_cmpstream_init", "gsv_cmpstream_push", "gsv_cmpstream_init_host", "gsv_cmpstream_push_host",
 ]
 
 
@@ -240,6 +241,17 @@ class CompressorRecord(ctypes.Structure):
 CMP_COMPRESSED, CMP_NONFINITE = 1, 4    # GSV_CMP_*
 CMP_RUN, CMP_SPAN, CMP_CHUNK = 16, 512 * 16, 2 * 512 * 16       # csrc/compressor.h: CMP_R, CMP_SPAN, CMP_CHUNK
 
+
+class CmpstreamRecord(ctypes.Structure):
+    """gsv_cmpstream_record: what one gsv_cmpstream_push emitted and found"""
+    _fields_ = [("emitted", ctypes.c_int32), ("flags", ctypes.c_int32), ("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float),
+                ("min_gain", ctypes.c_float), ("peak_in_run", ctypes.c_float), ("peak_out_run", ctypes.c_float),
+                ("min_gain_run", ctypes.c_float), ("total", ctypes.c_int64)]
+
+
+CMS_STREAM, CMS_NONFINITE_EVER, CMS_NONFINITE, CMS_COMPRESSED = 1, 2, 4, 8      # GSV_CMS_*
+CMS_MAX_CHUNK = 1 << 20                 # csrc/cmpstream.h: samples of one push
+
 FLAC_ENC_CONSTANT, FLAC_ENC_VERBATIM, FLAC_ENC_FIXED = range(3)     # GSV_FLAC_ENC_*
 FLAC_ENC_MAX_BLOCK = 4608
 
@@ -380,6 +392,10 @@ def lib():
         "gsv_compressor": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz, vp],
         "gsv_compressor_host": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz],
         "gsv_compressor_math_host": [i, vp, vp, sz],
+        "gsv_cmpstream_init": [vp, sz, ctypes.POINTER(CompressorParams), vp],
+        "gsv_cmpstream_push": [vp, vp, i, vp, i, vp, vp, vp],
+        "gsv_cmpstream_init_host": [vp, sz, ctypes.POINTER(CompressorParams)],
+        "gsv_cmpstream_push_host": [vp, vp, i, vp, i, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -430,6 +446,8 @@ def lib():
     L.gsv_compressor_work_bytes.restype = sz
     L.gsv_eqstream_state_bytes.argtypes = []
     L.gsv_eqstream_state_bytes.restype = sz
+    L.gsv_cmpstream_state_bytes.argtypes = []
+    L.gsv_cmpstream_state_bytes.restype = sz
     L.gsv_limstream_state_bytes.argtypes = [i, i]
     L.gsv_limstream_state_bytes.restype = sz
     L.gsv_limstream_out_capacity.argtypes = [i, i]

@@ -7,6 +7,7 @@ call, from zero state, in fp64, rounded once to fp32:
     clips, recs = compress([a, b, c], 32000, "voice")          # or one Compressor / preset name / None per clip
     recs[0].peak_in, recs[0].peak_out, recs[0].min_gain, recs[0].compressed
     out_db = curve(c, [-40.0, -18.0, 0.0])                     # the static curve, output level against input level
+    s = StreamCompressor("voice", 32000, "cuda"); y = s.push(chunk)    # a stream in pushes: the same bytes however it is cut
 
 With aA = exp(-2 pi 1000 / (rate attack_ms)) and aR likewise (JUCE's meaning of the two times, so attack_ms=1, release_ms=100 are
 pedalboard's defaults), T = 10^(threshold_db / 20), s = 1 / ratio - 1 and M = 10^(makeup_db / 20), per sample
@@ -241,3 +242,132 @@ def routine(which, values) -> np.ndarray:
     out = np.empty_like(v)
     N.check(N.lib().gsv_compressor_math_host({"log2": 0, "exp2": 1}[which], v.ctypes.data, out.ctypes.data, v.size))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# streams (csrc/cmpstream.h)
+# ----------------------------------------------------------------------------------------------------------------------
+_SREC = np.dtype([("emitted", "<i4"), ("flags", "<i4"), ("peak_in", "<f4"), ("peak_out", "<f4"), ("min_gain", "<f4"),
+                  ("peak_in_run", "<f4"), ("peak_out_run", "<f4"), ("min_gain_run", "<f4"), ("total", "<i8")])
+assert _SREC.itemsize == ctypes.sizeof(N.CmpstreamRecord)
+STREAM_RECORD_BYTES = _SREC.itemsize
+
+
+class CmpStreamRecord:
+    """emitted: samples the push handed out (as many as it took); total: samples of the stream so far; peak_in / peak_out: max |x|
+    and max |y| over the push's finite samples (np.float32, 0 for none), min_gain: the smallest gain among them, makeup excluded
+    (np.float32, 1 for none); peak_in_run / peak_out_run / min_gain_run: over the stream's so far; live: the record of a state
+    init made; compressed: min_gain is below 1; nonfinite: a NaN or an infinity among this push's samples (it ran through the
+    detector as 0.0 and was copied to the output), nonfinite_ever: among the stream's so far"""
+
+    __slots__ = ("emitted", "total", "peak_in", "peak_out", "min_gain", "peak_in_run", "peak_out_run", "min_gain_run", "live",
+                 "compressed", "nonfinite", "nonfinite_ever")
+
+    def __init__(self, emitted, flags, peak_in, peak_out, min_gain, peak_in_run, peak_out_run, min_gain_run, total):
+        self.emitted, self.total = int(emitted), int(total)
+        self.peak_in, self.peak_out, self.min_gain = np.float32(peak_in), np.float32(peak_out), np.float32(min_gain)
+        self.peak_in_run, self.peak_out_run = np.float32(peak_in_run), np.float32(peak_out_run)
+        self.min_gain_run = np.float32(min_gain_run)
+        self.live = flags >= 0 and bool(flags & N.CMS_STREAM)
+        self.compressed = flags >= 0 and bool(flags & N.CMS_COMPRESSED)
+        self.nonfinite = flags >= 0 and bool(flags & N.CMS_NONFINITE)
+        self.nonfinite_ever = flags >= 0 and bool(flags & N.CMS_NONFINITE_EVER)
+
+    def __repr__(self):
+        return ("CmpStreamRecord(emitted=%d, total=%d, peak_in=%r, peak_out=%r, min_gain=%r, peak_in_run=%r, peak_out_run=%r, "
+                "min_gain_run=%r, compressed=%r, nonfinite=%r, nonfinite_ever=%r)" % (
+                    self.emitted, self.total, float(self.peak_in), float(self.peak_out), float(self.min_gain), float(self.peak_in_run),
+                    float(self.peak_out_run), float(self.min_gain_run), self.compressed, self.nonfinite, self.nonfinite_ever))
+
+
+def stream_record(raw):
+    """the 40 record bytes (a tensor on any device, or a numpy array of them) -> CmpStreamRecord"""
+    raw = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else np.asarray(raw)
+    return CmpStreamRecord(*np.frombuffer(raw.tobytes()[:STREAM_RECORD_BYTES], dtype=_SREC)[0].tolist())
+
+
+class StreamCompressor:
+    """One stream through the compressor `c` -- a preset name or a Compressor -- at `rate`.  push(x, flush) -> float32
+    numpy, as many samples as went in: the compressor is causal, so there is no delay, and a flush hands out nothing extra; it ends
+    the stream, and the next push starts a fresh one with the same parameters.  The samples never depend on how the stream was cut
+    into pushes: concatenated they are `compress` of the concatenated input, bit for bit.  A NaN or an infinity runs through the
+    detector as 0.0 and is copied to the output.  On a GPU device a push is the six launches of `gsv_cmpstream_push`; on "cpu" the
+    host twin runs the same scalar routines and gives the same bytes."""
+
+    def __init__(self, c, rate: int, device="cpu"):
+        self.rate = _check_rate(rate)
+        self.compressor = resolve(c)
+        if self.compressor is None:
+            raise ValueError("a stream compressor needs a compressor that is not the identity")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        _, tab = _tables([], [], [], [self.compressor.coefficients(self.rate)])
+        L = N.lib()
+        nbytes = L.gsv_cmpstream_state_bytes()
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                N.check(L.gsv_cmpstream_init(self.state.data_ptr(), nbytes, tab, N.current_stream_ptr(self.device)))
+        else:
+            N.check(L.gsv_cmpstream_init_host(self.state.data_ptr(), nbytes, tab))
+        self._rec = None        # the last push's record
+
+    @property
+    def on_device(self) -> bool:
+        return self.device.type == "cuda"
+
+    def enqueue(self, chunk_ptr: int, n_cap: int, n_dev_ptr, flush: bool, out_ptr: int, rec_ptr: int):
+        """the raw device call on the current stream: nothing is read back (ChunkEmitter's use); out_ptr may be chunk_ptr"""
+        N.check(N.lib().gsv_cmpstream_push(self.state.data_ptr(), chunk_ptr or None, int(n_cap), n_dev_ptr, int(bool(flush)),
+                                           out_ptr or None, rec_ptr, N.current_stream_ptr(self.device)))
+
+    def _push_once(self, x: torch.Tensor, flush: bool):
+        n = int(x.numel())
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        rec = torch.empty(STREAM_RECORD_BYTES // 8, dtype=torch.int64, device=self.device)      # 8-byte aligned
+        if self.on_device:
+            with torch.cuda.device(self.device):
+                self.enqueue(x.data_ptr(), n, None, flush, out.data_ptr(), rec.data_ptr())
+        else:
+            N.check(N.lib().gsv_cmpstream_push_host(self.state.data_ptr(), x.data_ptr() or None, n, None, int(bool(flush)),
+                                                    out.data_ptr() or None, rec.data_ptr()))
+        return out, rec
+
+    def push_tensor(self, x: torch.Tensor, flush: bool = False) -> torch.Tensor:
+        """x on the compressor's device -> the compressed samples, a new fp32 tensor there of x's length.  The record is read, so
+        the call waits for the push.  Input longer than one push may be (2^20 samples) goes in as several, which changes no byte;
+        `rec` is then the last one's."""
+        x = x.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        parts = []
+        cuts = list(range(0, int(x.numel()), N.CMS_MAX_CHUNK)) or [0]
+        for k, at in enumerate(cuts):
+            out, rec = self._push_once(x[at: at + N.CMS_MAX_CHUNK], flush and k + 1 == len(cuts))
+            self._rec = stream_record(rec.view(torch.uint8))
+            parts.append(out[: self._rec.emitted])
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def push(self, x, flush: bool = False) -> np.ndarray:
+        return self.push_tensor(torch.as_tensor(x), flush).cpu().numpy()
+
+    @property
+    def rec(self):
+        """the last push's CmpStreamRecord (None before the first push)"""
+        return self._rec
+
+
+def compress_stream(x, rate, c, cuts=None, device=None):
+    """the whole signal compressed as one stream on the CPU's host twin (the GPU gives the same bytes: name a device to run there)
+    -> (float32 numpy, the last push's CmpStreamRecord).  cuts: the lengths of the pushes to cut it into (they must add up to the
+    signal's; an empty push is legal), default one push; the last one flushes.  However it is cut, the samples are
+    `compress(x, rate, c)`'s."""
+    x = np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
+    cuts = [len(x)] if cuts is None else [int(v) for v in cuts]
+    if any(v < 0 for v in cuts) or sum(cuts) != len(x) or not cuts:
+        raise ValueError("compress: cuts of %r for %d samples" % (cuts, len(x)))
+    st = StreamCompressor(c, rate, torch.device("cpu") if device is None else device)
+    parts, at = [], 0
+    for k, v in enumerate(cuts):
+        parts.append(st.push(x[at: at + v], flush=k + 1 == len(cuts)))
+        at += v
+    return np.concatenate(parts), st.rec

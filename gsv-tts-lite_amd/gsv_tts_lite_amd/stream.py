@@ -12,7 +12,9 @@ the device, and the samples reach the host by one asynchronous copy behind a han
 packets of a real-time track are made behind it by `gsv_track_push`, which reads the chunk's length from the emit record on the
 device, and travel in the same copy.  With a `level` (level.StreamLeveller) the emitted samples are levelled in place by
 `gsv_level_push` between the two, the same way: a track then carries levelled audio.  With an `eq` (eq.StreamEQ) they are equalised
-in place by `gsv_eqstream_push` first of all, so the leveller measures equalised audio as `loudness=` does on clips."""
+in place by `gsv_eqstream_push` first of all, so the leveller measures equalised audio as `loudness=` does on clips.  With a
+`compress` (compressor.StreamCompressor) they are compressed in place by `gsv_cmpstream_push` behind the equaliser and in front of
+the leveller: the clip path's order."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -60,8 +62,10 @@ class ChunkSplicer:
 class _Emitted:
     """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
 
-    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None, eq_at=None):
+    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None, eq_at=None, comp_at=None):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
+        self._comp_at = comp_at     # with a compressor: where its record starts in the buffer (fp32 elements)
+        self.comp = None            # and the record itself (compressor.CmpStreamRecord), once result() has been called
         self._eq_at = eq_at         # with an equaliser: where its record starts in the buffer (fp32 elements)
         self.eq = None              # and the record itself (eq.EqStreamRecord), once result() has been called
         self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
@@ -85,6 +89,10 @@ class _Emitted:
             if self._eq_at is not None:
                 from . import eq
                 self.eq = eq.stream_record(host[self._eq_at: self._eq_at + eq.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
+            if self._comp_at is not None:
+                from . import compressor
+                at = self._comp_at
+                self.comp = compressor.stream_record(host[at: at + compressor.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
             if self._level_at is not None:
                 from . import level
                 self.level = level.record(host[self._level_at: self._level_at + level.RECORD_BYTES // 4].numpy().view("uint8"))
@@ -131,11 +139,18 @@ class ChunkEmitter:
     number read from its record on the device; the stages behind read their length from the equaliser's record, which rides
     8-byte aligned behind the samples in the same buffer and the same copy, and the handle carries it in `eq`.  Its state spans
     the text like the others', and `flush` ends its stream too.  Without one the buffer's layout and every byte are what they
-    were."""
+    were.
 
-    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None, eq=None):
+    compress: a compressor.StreamCompressor on the chunks' device, or None.  With one, push() enqueues `gsv_cmpstream_push` behind
+    the equaliser and in front of the leveller (emit -> eq -> compress -> level -> limit -> track, the clip path's order), in place
+    on the same samples, their number read on the device from the record of the stage in front; the stages behind read their
+    length from the compressor's record, which rides 8-byte aligned in the same buffer and the same copy, and the handle carries
+    it in `comp`.  Its state spans the text like the others', and `flush` ends its stream too.  Without one the buffer's layout
+    and every byte are what they were."""
+
+    def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None, eq=None, compress=None):
         self.overlap, self.search_len, self.track, self.level, self.limit = int(overlap_samples), int(search_len), track, level, limit
-        self.eq = eq
+        self.eq, self.compress = eq, compress
         self._tails, self._cur, self._ws = None, None, None      # _cur: index of the tail the next splice reads, None: no tail yet
         self._free = []             # (device fp32 [4 + capacity]: rec, out; its pinned twin), not in flight
 
@@ -164,21 +179,27 @@ class ChunkEmitter:
         lim_cap = 0 if self.limit is None else self.limit.capacity(used - 4)     # the most samples the limiter emits
         pcm_cap = 0 if self.track is None else (self.track.capacity(lim_cap or used - 4) + 1) // 2      # int16 pairs as fp32 elements
         erec = 0 if self.eq is None else (used & 1) + 8           # the equaliser's record, 8-byte aligned, as fp32 elements
-        lrec = 0 if self.level is None else ((used + erec) & 1) + 10      # the level record, 8-byte aligned
-        mrec = 0 if self.limit is None else ((used + erec + lrec) & 1) + 8 + lim_cap       # the limiter's record, 8-byte aligned, and its samples
-        dbuf, hbuf = bufs = self._buffers(used + erec + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
+        crec = 0 if self.compress is None else ((used + erec) & 1) + 10   # the compressor's record, 8-byte aligned
+        lrec = 0 if self.level is None else ((used + erec + crec) & 1) + 10       # the level record, 8-byte aligned
+        mrec = 0 if self.limit is None else ((used + erec + crec + lrec) & 1) + 8 + lim_cap    # the limiter's record, 8-byte aligned, and its samples
+        dbuf, hbuf = bufs = self._buffers(used + erec + crec + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
                                   int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
                                   self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        pcm_at, level_at, limit_at, eq_at, n_samples = None, None, None, None, used - 4
+        pcm_at, level_at, limit_at, eq_at, comp_at, n_samples = None, None, None, None, None, used - 4
         src, src_cap, src_len = dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr()       # what the next stage reads: samples, capacity, length
         if self.eq is not None:          # [rec 4 | samples | eq rec 8 (8-byte aligned) | ...]: in place, first of all
             eq_at = used + (used & 1)
             self.eq.enqueue(src, n_samples, src_len, flush, src, dbuf[eq_at:].data_ptr())
             src_len = dbuf[eq_at:].data_ptr()
             used += erec
+        if self.compress is not None:    # [... | compressor rec 10 (8-byte aligned) | ...]: in place, behind the equaliser
+            comp_at = used + (used & 1)
+            self.compress.enqueue(src, n_samples, src_len, flush, src, dbuf[comp_at:].data_ptr())
+            src_len = dbuf[comp_at:].data_ptr()
+            used += crec
         if self.level is not None:       # [rec 4 | samples | level rec 10 (8-byte aligned) | ...]: in place, before the track reads them
             level_at = used + (used & 1)
             self.level.enqueue(dbuf[4:].data_ptr(), n_samples, src_len, flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
@@ -196,4 +217,4 @@ class ChunkEmitter:
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at, eq_at)
+        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at, eq_at, comp_at)

@@ -106,7 +106,8 @@ class AudioClip:
         self.eq = None              # a clip made with eq= (or by equalised()): the eq.EqRecord -- peak_in, peak_out, sections;
                                     # a clip of a stream made with eq=: the eq.EqStreamRecord of its push
         self.comp = None            # a clip made with compress= (or by compressed()): the compressor.CmpRecord -- peak_in, peak_out,
-                                    # min_gain, compressed
+                                    # min_gain, compressed; a clip of a stream made with compress=: the
+                                    # compressor.CmpStreamRecord of its push
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -321,17 +322,20 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None, eq=None):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None, eq=None,
+                 compress=None):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        # the text's own TrackResampler / StreamLeveller / StreamLimiter / StreamEQ, or None (without a limiter or an equaliser: the
-        # call as it always was)
+        # the text's own TrackResampler / StreamLeveller / StreamLimiter / StreamEQ / StreamCompressor, or None (without a limiter,
+        # an equaliser or a compressor: the call as it always was)
         stages = {} if limit is None else {"limit": limit}
         if eq is not None:
             stages["eq"] = eq
+        if compress is not None:
+            stages["compress"] = compress
         self.emitter = ChunkEmitter(overlap_samples, track=track, level=level, **stages)
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
@@ -1121,7 +1125,8 @@ class TTS:
                                          "，": 1.0, ":": 1.0, "：": 1.0, ";": 1.0, "；": 1.0, "~": 1.0, "、": 0.8, "・": 0.8},
                      stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                      temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None, true_peak=None, eq=None):
+                     sovits_model=None, debug=True, track=None, loudness=None, loudness_seed=None, true_peak=None, eq=None,
+                     compress=None):
         """TTS.py:289-504: generator of AudioClip chunks.  Per text segment the GPT streams cumulative token
         chunks (t2s.infer_stream); every chunk is decoded from the start of the segment with
         decode(stream_mode=True) -- only frames past `valid_start_idx` reach the flow / Generator -- and joined
@@ -1158,9 +1163,18 @@ class TTS:
         equalised audio.  An equaliser is causal: no delay, the clips keep their lengths.  Each clip carries `eq`, the
         eq.EqStreamRecord: the peaks before and after of its samples and of the stream so far, which nothing clamps (peak_out_run
         may exceed 1.0; true_peak= holds a ceiling), and `total`, the stream's samples so far.  An EQ that is the identity is as
-        no EQ."""
+        no EQ.
+
+        compress: None, a preset name ("voice") or a compressor.Compressor: the text's audio -- one stream, as for loudness= -- goes
+        through the stream compressor on the device (compressor.StreamCompressor) behind the equaliser and ahead of
+        the leveller and the limiter, the clip path's order (eq -> compress -> level -> limit -> track): the concatenated
+        audio_data is compressor.compress() of the concatenated uncompressed clips, bit for bit.  The compressor is causal: no
+        delay, the clips keep their lengths.  Each clip carries `comp`, the compressor.CmpStreamRecord: the peaks before and after
+        and the smallest gain of its samples and of the stream so far, and `total`, the stream's samples so far.  A compressor
+        that is the identity is as none."""
         loudness, loudness_seed, true_peak = _check_loudness(loudness), _check_loudness_seed(loudness_seed), _check_true_peak(true_peak)
         eq = _check_eq(eq, self.samplerate)
+        compress = _check_compress(compress)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -1190,6 +1204,7 @@ class TTS:
                 leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev, true_peak is not None)
                 limiter = None if true_peak is None else self._limiter(true_peak, dev)
                 equaliser = None if eq is None else self._equaliser(eq, dev)
+                squeezer = None if compress is None else self._stream_compressor(compress, dev)
                 for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
@@ -1238,6 +1253,8 @@ class TTS:
                                     new_subtitles[-1]["end_s"] = None
                             if equaliser is not None:
                                 audio = equaliser.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
+                            if squeezer is not None:
+                                audio = squeezer.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             if leveller is not None:
                                 audio = leveller.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             if limiter is not None:
@@ -1248,6 +1265,8 @@ class TTS:
                         clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
                         if equaliser is not None:
                             clip.eq = equaliser.rec
+                        if squeezer is not None:
+                            clip.comp = squeezer.rec
                         if leveller is not None:
                             _with_level(clip, leveller.rec)
                         if limiter is not None:
@@ -1280,6 +1299,10 @@ class TTS:
         from .eq import StreamEQ
         return StreamEQ(eq, self.samplerate, dev)
 
+    def _stream_compressor(self, c, dev):
+        from .compressor import StreamCompressor
+        return StreamCompressor(c, self.samplerate, dev)
+
     def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
                              is_cut_text=True, cut_minlen=10, cut_mute=0.4,
                              cut_mute_scale_map={"…": 2.0, ".": 1.5, "。": 1.5, "?": 1.5, "？": 1.5, "!": 1.5, "！": 1.5,
@@ -1288,7 +1311,7 @@ class TTS:
                              stream_mode="token", stream_chunk=25, overlap_len=5, boost_first_chunk=True, top_k=15, top_p=1.0,
                              temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
                              sovits_model=None, debug=True, slots=None, seed=None, track=None, loudness=None, loudness_seed=None,
-                             true_peak=None, eq=None):
+                             true_peak=None, eq=None, compress=None):
         """`infer_stream` for many texts at once: a generator of (text index, AudioClip).  Per text the clips are the ones
         `infer_stream` yields for that text -- audio, audio_len_s, subtitles, in that order (equal bit for bit for greedy fp32
         requests that end with an EOS and noise_scale 0) --; texts interleave as their chunks become ready.
@@ -1321,7 +1344,12 @@ class TTS:
         eq: as in `infer_stream`, None, a preset name or an eq.EQ for every text, or a list with one of those per TEXT (a wrong
         length raises ValueError; a bare list of eq.Band objects is not an equaliser: wrap it in eq.EQ).  Every text with one has
         its own equaliser state, enqueued directly behind the chunk's epilogue, in place and in front of the leveller, with the
-        chunk's length read on the device: the loop still waits for nothing, and a text with None gets the clips it gets today."""
+        chunk's length read on the device: the loop still waits for nothing, and a text with None gets the clips it gets today.
+
+        compress: as in `infer_stream`, None, a preset name or a compressor.Compressor for every text, or a list with one of those
+        per TEXT (a wrong length raises ValueError).  Every text with one has its own compressor state, enqueued behind the
+        equaliser and in front of the leveller, in place, with the chunk's length read on the device from the stage in front: the
+        loop still waits for nothing, and a text with None gets the clips it gets today."""
         with self._infer_lock:
             vq, gen = None, None
             try:
@@ -1336,6 +1364,9 @@ class TTS:
                 if isinstance(eq, (list, tuple)) and len(eq) != n:
                     raise ValueError("eq has %d entries for %d requests" % (len(eq), n))
                 eq = [_check_eq(v, self.samplerate) for v in (eq if isinstance(eq, (list, tuple)) else [eq] * n)]
+                if isinstance(compress, (list, tuple)) and len(compress) != n:
+                    raise ValueError("compress has %d entries for %d requests" % (len(compress), n))
+                compress = [_check_compress(v) for v in (compress if isinstance(compress, (list, tuple)) else [compress] * n)]
                 speed = slot_sampling.per_request("speed", speed, n)
                 noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
                 if not all(s > 0 for s in speed):
@@ -1372,7 +1403,8 @@ class TTS:
                                            None if loudness[t] is None else
                                            self._leveller(loudness[t], loudness_seed[t], dev, true_peak[t] is not None),
                                            None if true_peak[t] is None else self._limiter(true_peak[t], dev),
-                                           None if eq[t] is None else self._equaliser(eq[t], dev)))
+                                           None if eq[t] is None else self._equaliser(eq[t], dev),
+                                           None if compress[t] is None else self._stream_compressor(compress[t], dev)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1493,6 +1525,8 @@ class TTS:
         clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
         if handle.eq is not None:
             clip.eq = handle.eq
+        if handle.comp is not None:
+            clip.comp = handle.comp
         if handle.level is not None:
             _with_level(clip, handle.level)
         if handle.limit is not None:

@@ -756,6 +756,47 @@ int gsv_eqstream_init_host(void* state, size_t bytes, const gsv_eq_design* desig
 int gsv_eqstream_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
                            gsv_eqstream_record* rec);
 
+/* Stream compressor: the compressor above for a stream that arrives in pushes (csrc/cmpstream.h).  The compressor
+ * is causal: a push of n samples emits n samples (no delay), a flush emits nothing extra (no ring-out) and returns the state to
+ * fresh, so that the next push starts a new stream with the same parameters.  The emitted samples, concatenated, are the bytes
+ * gsv_compressor / gsv_compressor_host return for the same finite samples as one clip with the same parameters, however the
+ * stream was cut into pushes: the stream runs the clip kernels' three passes and two chains on 16384-sample chunks aligned to
+ * the stream index, and a chunk a push leaves unfinished is redone from its start states over its kept input.  A sample that is
+ * not finite enters the detector as 0.0 and is copied to the output bit for bit (GSV_CMS_NONFINITE on the push,
+ * GSV_CMS_NONFINITE_EVER on the stream); it is kept out of the peaks and of the smallest gain, and every other output equals the
+ * stream with that sample replaced by 0.0.
+ *   state: caller-owned, gsv_cmpstream_state_bytes() bytes, 16-byte aligned, made by gsv_cmpstream_init from one parameter set
+ *   (HOST memory in both entries): a header, the coefficients and their powers, the open chunk's start states of the release and
+ *   the attack, the open chunk's input so far in two copies used in turn, and the per-push scratch of the chunk states.
+ *   gsv_cmpstream_push: chunk fp32 [n_cap], n_cap 0..2^20 (chunk and out may be NULL at 0); n_dev NULL or a device int32 holding
+ *   the real length (clamped to 0..n_cap), e.g. gsv_stream_emit's or gsv_eqstream_push's record; out fp32 [n_cap], which may be
+ *   chunk (in place): the first `emitted` are written, nothing behind them; rec (device, 8-byte aligned).  Six launches whatever
+ *   the length (three at n_cap 0), nothing allocated, nothing read by the host.  A state gsv_cmpstream_init did not make is not
+ *   read through: flags -1, out not written.
+ *   gsv_cmpstream_init_host / gsv_cmpstream_push_host: the same over HOST memory from the same scalar routines -- the CPU path
+ *   and the device's oracle (device samples and records equal the host's bit for bit); they need no GPU.
+ * GSV_ERR_ARG: a null pointer, a size that is negative or above 2^20, parameters gsv_compressor would refuse, a state that is too
+ * small or misaligned, a misaligned record. */
+typedef struct {
+    int32_t emitted;            /* samples this push wrote to out: its address serves as the next stage's n_dev */
+    int32_t flags;
+    float peak_in, peak_out;    /* max |x|, max |y| over the finite samples of this push (0: none) */
+    float min_gain;             /* the smallest gain (makeup excluded) among them (1: none) */
+    float peak_in_run, peak_out_run, min_gain_run;      /* ... of the stream so far */
+    int64_t total;              /* samples of the stream so far (a flush reports the stream's length) */
+} gsv_cmpstream_record;
+#define GSV_CMS_STREAM 1            /* the record of a state gsv_cmpstream_init made */
+#define GSV_CMS_NONFINITE_EVER 2    /* a NaN or an infinity among the stream's samples so far */
+#define GSV_CMS_NONFINITE 4         /* ... among this push's samples */
+#define GSV_CMS_COMPRESSED 8        /* min_gain < 1: the compressor acted on this push */
+size_t gsv_cmpstream_state_bytes(void);
+int gsv_cmpstream_init(void* state, size_t bytes, const gsv_compressor_params* params, void* stream);
+int gsv_cmpstream_push(void* state, const float* chunk, int n_cap, const int32_t* n_dev, int flush, float* out,
+                       gsv_cmpstream_record* rec, void* stream);
+int gsv_cmpstream_init_host(void* state, size_t bytes, const gsv_compressor_params* params);
+int gsv_cmpstream_push_host(void* state, const float* chunk, int n_cap, const int32_t* n_host, int flush, float* out,
+                            gsv_cmpstream_record* rec);
+
 /* Reference-audio path, once per new speaker / prompt; fp32 in both numerics modes.
  * Replaces, on the device:
  *   gsv_ref_spectrogram     the torchaudio Spectrogram inside TTS._get_spec (gsv_tts/TTS.py:1591-1604: n_fft /
