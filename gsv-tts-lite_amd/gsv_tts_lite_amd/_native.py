@@ -46,6 +46,7 @@ EXPORTS = [
     "gsv_eqstream_state_bytes", "gsv_eqstream_init", "gsv_eqstream_push", "gsv_eqstream_init_host", "gsv_eqstream_push_host",
     "gsv_compressor_work_bytes", "gsv_compressor", "gsv_compressor_host", "gsv_compressor_math_host",
     "gsv_cmpstream_state_bytes", "gsv_cmpstream_init", "gsv_cmpstream_push", "gsv_cmpstream_init_host", "gsv_cmpstream_push_host",
+    "gsv_reverb_work_bytes", "gsv_reverb", "gsv_reverb_host",
 ]
 
 
@@ -242,6 +243,27 @@ CMP_COMPRESSED, CMP_NONFINITE = 1, 4    # GSV_CMP_*
 CMP_RUN, CMP_SPAN, CMP_CHUNK = 16, 512 * 16, 2 * 512 * 16       # csrc/compressor.h: CMP_R, CMP_SPAN, CMP_CHUNK
 
 
+class ReverbClip(ctypes.Structure):
+    """gsv_reverb_clip: one clip of gsv_reverb; params -1: measure the peaks, copy"""
+    _fields_ = [("offset", ctypes.c_int64), ("n_samples", ctypes.c_int32), ("params", ctypes.c_int32)]
+
+
+class ReverbParams(ctypes.Structure):
+    """gsv_reverb_params: the eight comb and four all-pass delays in samples, damping, feedback, the input, wet and dry gains"""
+    _fields_ = [("comb", ctypes.c_int32 * 8), ("allpass", ctypes.c_int32 * 4), ("d", ctypes.c_double), ("fb", ctypes.c_double),
+                ("gin", ctypes.c_double), ("gw", ctypes.c_double), ("gd", ctypes.c_double)]
+
+
+class ReverbRecord(ctypes.Structure):
+    """gsv_reverb_record: what gsv_reverb found and did per clip"""
+    _fields_ = [("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float), ("flags", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+RVB_REVERBED, RVB_NONFINITE = 1, 4      # GSV_RVB_*
+RVB_MAX_DELAY = 32768                   # GSV_RVB_MAX_DELAY
+RVB_SPAN = 64 * 32                      # csrc/reverb.h: RVB_SPAN, the longest line a comb's wave keeps in registers
+
+
 class CmpstreamRecord(ctypes.Structure):
     """gsv_cmpstream_record: what one gsv_cmpstream_push emitted and found"""
     _fields_ = [("emitted", ctypes.c_int32), ("flags", ctypes.c_int32), ("peak_in", ctypes.c_float), ("peak_out", ctypes.c_float),
@@ -392,6 +414,8 @@ def lib():
         "gsv_compressor": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz, vp],
         "gsv_compressor_host": [vp, sz, ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i, vp, vp, vp, sz],
         "gsv_compressor_math_host": [i, vp, vp, sz],
+        "gsv_reverb": [vp, sz, ctypes.POINTER(ReverbClip), i, ctypes.POINTER(ReverbParams), i, vp, vp, vp, sz, vp],
+        "gsv_reverb_host": [vp, sz, ctypes.POINTER(ReverbClip), i, ctypes.POINTER(ReverbParams), i, vp, vp, vp, sz],
         "gsv_cmpstream_init": [vp, sz, ctypes.POINTER(CompressorParams), vp],
         "gsv_cmpstream_push": [vp, vp, i, vp, i, vp, vp, vp],
         "gsv_cmpstream_init_host": [vp, sz, ctypes.POINTER(CompressorParams)],
@@ -444,6 +468,8 @@ def lib():
     L.gsv_eq_work_bytes.restype = sz
     L.gsv_compressor_work_bytes.argtypes = [ctypes.POINTER(CompressorClip), i, ctypes.POINTER(CompressorParams), i]
     L.gsv_compressor_work_bytes.restype = sz
+    L.gsv_reverb_work_bytes.argtypes = [ctypes.POINTER(ReverbClip), i, ctypes.POINTER(ReverbParams), i]
+    L.gsv_reverb_work_bytes.restype = sz
     L.gsv_eqstream_state_bytes.argtypes = []
     L.gsv_eqstream_state_bytes.restype = sz
     L.gsv_cmpstream_state_bytes.argtypes = []

@@ -108,6 +108,8 @@ class AudioClip:
         self.comp = None            # a clip made with compress= (or by compressed()): the compressor.CmpRecord -- peak_in, peak_out,
                                     # min_gain, compressed; a clip of a stream made with compress=: the
                                     # compressor.CmpStreamRecord of its push
+        self.ambience = None        # a clip made with ambience= (or by ambient()): the reverb.RvbRecord -- peak_in, peak_out,
+                                    # reverbed
 
     def play(self, volume: float = 1.0):
         if self.audio_queue is None:
@@ -155,7 +157,7 @@ class AudioClip:
         from . import loudness
         audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp = self.eq, self.comp
+        out.eq, out.comp, out.ambience = self.eq, self.comp, self.ambience
         return _with_loudness(out, rec)
 
     def equalised(self, eq="voice") -> "AudioClip":
@@ -166,7 +168,7 @@ class AudioClip:
             raise ValueError("eq: a preset name (%s) or an eq.EQ, not %r" % (", ".join(eqm.PRESETS), type(eq).__name__))
         audio, rec = eqm.equalise(self.audio_data, self.samplerate, eq)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp = rec, self.comp
+        out.eq, out.comp, out.ambience = rec, self.comp, self.ambience
         return out
 
     def compressed(self, c="voice") -> "AudioClip":
@@ -178,7 +180,19 @@ class AudioClip:
             raise ValueError("compress: a preset name (%s) or a compressor.Compressor, not %r" % (", ".join(cm.PRESETS), type(c).__name__))
         audio, rec = cm.compress(self.audio_data, self.samplerate, c)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp = self.eq, rec
+        out.eq, out.comp, out.ambience = self.eq, rec, self.ambience
+        return out
+
+    def ambient(self, r="voice") -> "AudioClip":
+        """a new clip through the reverb `r` -- a reverb.Reverb or a preset name (reverb.py) --, same subtitles, text
+        and length (the tail behind the clip is cut); its `ambience` is the reverb.RvbRecord: the peak before and after, which the
+        dry gain may lift above 1.0 (limited_to() holds a ceiling); `eq` and `comp` are kept"""
+        from . import reverb as rv
+        if not isinstance(r, (str, rv.Reverb)):
+            raise ValueError("ambience: a preset name (%s) or a reverb.Reverb, not %r" % (", ".join(rv.PRESETS), type(r).__name__))
+        audio, rec = rv.reverberate(self.audio_data, self.samplerate, r)
+        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
+        out.eq, out.comp, out.ambience = self.eq, self.comp, rec
         return out
 
     def true_peak(self) -> float:
@@ -193,7 +207,7 @@ class AudioClip:
         from . import limiter
         audio, rec = limiter.limit(self.audio_data, self.samplerate, ceiling_db)
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.lufs, out.gain, out.eq, out.comp = self.lufs, self.gain, self.eq, self.comp
+        out.lufs, out.gain, out.eq, out.comp, out.ambience = self.lufs, self.gain, self.eq, self.comp, self.ambience
         return _with_true_peak(out, rec)
 
     def _save_wav(self, save_path):
@@ -209,9 +223,10 @@ def _with_loudness(clip, rec):
     return clip
 
 
-def _with_records(clip, rec, lim, eqr=None, comp=None):
-    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr), compress= (comp) or several of them"""
-    clip.eq, clip.comp = eqr, comp
+def _with_records(clip, rec, lim, eqr=None, comp=None, amb=None):
+    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr), compress= (comp), ambience= (amb) or several
+    of them"""
+    clip.eq, clip.comp, clip.ambience = eqr, comp, amb
     if rec is not None:
         _with_loudness(clip, rec)
     return clip if lim is None else _with_true_peak(clip, lim)
@@ -241,6 +256,14 @@ def _check_compress(v):
         return None
     from . import compressor
     return compressor.resolve(v)
+
+
+def _check_ambience(v):
+    """an ambience= value: None, a preset name or a reverb.Reverb -> None (also for the identity) or the Reverb"""
+    if v is None:
+        return None
+    from . import reverb
+    return reverb.resolve(v)
 
 
 def _with_level(clip, rec):
@@ -923,7 +946,7 @@ class TTS:
     @torch.inference_mode()
     def infer(self, spk_audio_path, prompt_audio_path, prompt_audio_text, text, return_subtitles=False, top_k=15,
               top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0, gpt_model=None,
-              sovits_model=None, loudness=None, true_peak=None, eq=None, compress=None):
+              sovits_model=None, loudness=None, true_peak=None, eq=None, compress=None, ambience=None):
         """eq: None, a preset name ("voice": the three filters of the reference WebUI's enhance_audio) or an eq.EQ: the clip that
         would have been returned -- after the peak rule, trailing 0.2 s of zeros included -- goes through that equaliser on the
         device before the download (eq.py), ahead of loudness= and true_peak= as in the reference's chain; the clip
@@ -934,6 +957,11 @@ class TTS:
         ahead of loudness= and true_peak=, the reference's order; the clip then carries `comp`, the record with the peaks, the
         smallest gain and whether the compressor acted.
 
+        ambience: None, a preset name ("voice": room 0.1, damping 0.5, 3 % wet, 97 % dry, the reverb of enhance_audio) or a
+        reverb.Reverb: the clip goes through that Freeverb on the device (reverb.py) behind compress= and ahead of
+        loudness= and true_peak=, the reference's order; it keeps its length, and carries `ambience`, the record with the peak
+        before and after.  Nothing clamps that peak (the preset's dry gain is 1.94): loudness= and true_peak= set the level.
+
         loudness: None, or a target in LUFS (-18.0 is the reference WebUI's): the clip that would have been returned -- after the
         peak rule, trailing 0.2 s of zeros included -- is measured and scaled to it on the device before the download
         (loudness.py); the clip then carries lufs (before the gain), gain and limited.
@@ -943,7 +971,7 @@ class TTS:
         limited (the limiter acted).  With loudness= as well the gain to the target is applied whatever the peak becomes, and the
         limiter then holds the ceiling: the loudness that comes out is what the limiter leaves."""
         loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
-        compress = _check_compress(compress)
+        compress, ambience = _check_compress(compress), _check_ambience(ambience)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -979,10 +1007,10 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
-                if loudness is not None or true_peak is not None or eq is not None or compress is not None:
-                    audio, rec, lim, eqr, comp = self._finish_on_device(audio.float(), loudness, true_peak, eq, compress)
+                if loudness is not None or true_peak is not None or eq is not None or compress is not None or ambience is not None:
+                    audio, rec, lim, eqr, comp, amb = self._finish_on_device(audio.float(), loudness, true_peak, eq, compress, ambience)
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text),
-                                         rec, lim, eqr, comp)
+                                         rec, lim, eqr, comp, amb)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -992,25 +1020,27 @@ class TTS:
             finally:
                 self._empty_cache()
 
-    def _finish_on_device(self, audio, target, ceiling=None, eq=None, compress=None):
-        """the tail of infer / infer_vc with eq=, compress=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1):
+    def _finish_on_device(self, audio, target, ceiling=None, eq=None, compress=None, ambience=None):
+        """the tail of infer / infer_vc with eq=, compress=, ambience=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1):
         dividing by 1 is exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then
-        one gsv_eq call (eq), one gsv_compressor call (compress), one gsv_loudness call (target) and one gsv_limiter call (ceiling)
-        over the finished clip in place -- the order of the reference's chain --, their records written behind the samples: ONE
-        download carries all -> (numpy samples, loudness record or None, limiter record or None, eq record or None, compressor
-        record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
+        one gsv_eq call (eq), one gsv_compressor call (compress), one gsv_reverb call (ambience), one gsv_loudness call (target) and
+        one gsv_limiter call (ceiling) over the finished clip in place -- the order of the reference's chain --, their records
+        written behind the samples: ONE download carries all -> (numpy samples, loudness record or None, limiter record or None,
+        eq record or None, compressor record or None, reverb record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
         ceiling."""
         from . import compressor as cm
         from . import eq as eqm
         from . import limiter as lm
         from . import loudness as ld
+        from . import reverb as rv
         if audio.numel():
             audio = audio / audio.abs().max().clamp(min=1)
         n = audio.numel() + int(0.2 * self.samplerate)
         words = (ld.RECORD_BYTES // 4 if target is not None else 0) + (lm.RECORD_BYTES // 4 if ceiling is not None else 0)
         eq_words = eqm.RECORD_BYTES // 4 if eq is not None else 0              # in front of the other two: 16 bytes keep their alignment
         cm_words = cm.RECORD_BYTES // 4 if compress is not None else 0         # and so do these 16
-        words += eq_words + cm_words
+        rv_words = rv.RECORD_BYTES // 4 if ambience is not None else 0         # and these
+        words += eq_words + cm_words + rv_words
         tail = (n + 1) // 2 * 2 - audio.numel() + words                        # zeros to n, to an 8-byte boundary, the records
         buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
         at = buf.numel() - words
@@ -1020,6 +1050,9 @@ class TTS:
         if compress is not None:
             cm.run_packed(buf[:n], [0], [n], [0], [compress.coefficients(self.samplerate)], buf[:n], buf[at: at + cm_words].view(torch.uint8))
         cmr_at, at = at, at + cm_words
+        if ambience is not None:
+            rv.run_packed(buf[:n], [0], [n], [0], [ambience.parameters(self.samplerate)], buf[:n], buf[at: at + rv_words].view(torch.uint8))
+        rvr_at, at = at, at + rv_words
         if target is not None:
             ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0 if ceiling is None else math.inf, buf[:n],
                           buf[at: at + ld.RECORD_BYTES // 4].view(torch.uint8))
@@ -1031,17 +1064,18 @@ class TTS:
         lim = lm.records(host[host.size - lm.RECORD_BYTES // 4:].view(np.uint8))[0] if ceiling is not None else None
         eqr = eqm.records(host[eqr_at: eqr_at + eq_words].view(np.uint8))[0] if eq is not None else None
         comp = cm.records(host[cmr_at: cmr_at + cm_words].view(np.uint8))[0] if compress is not None else None
-        return host[:n], rec, lim, eqr, comp
+        amb = rv.records(host[rvr_at: rvr_at + rv_words].view(np.uint8))[0] if ambience is not None else None
+        return host[:n], rec, lim, eqr, comp, amb
 
     @torch.inference_mode()
     def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
-                 loudness=None, true_peak=None, eq=None, compress=None):
+                 loudness=None, true_peak=None, eq=None, compress=None, ambience=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
         decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
-        loudness, true_peak, eq, compress: as in infer."""
+        loudness, true_peak, eq, compress, ambience: as in infer."""
         loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
-        compress = _check_compress(compress)
-        finish = loudness is not None or true_peak is not None or eq is not None or compress is not None
+        compress, ambience = _check_compress(compress), _check_ambience(ambience)
+        finish = loudness is not None or true_peak is not None or eq is not None or compress is not None or ambience is not None
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -1059,7 +1093,7 @@ class TTS:
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
                 if finish:
-                    audio, rec, lim, eqr, comp = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq, compress)
+                    audio, rec, lim, eqr, comp, amb = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq, compress, ambience)
                 else:
                     audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
@@ -1067,7 +1101,7 @@ class TTS:
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
                 if finish:
                     return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
-                                                   prompt_audio_text), rec, lim, eqr, comp)
+                                                   prompt_audio_text), rec, lim, eqr, comp, amb)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1567,7 +1601,7 @@ class TTS:
                                           "、": 0.8, "・": 0.8},
                       top_k=15, top_p=1.0, temperature=1.0, repetition_penalty=1.35, noise_scale=0.5, speed=1.0,
                       bert_batch_size=20, sovits_batch_size=10, gpt_model=None, sovits_model=None, seed=None,
-                      initial_suppression_steps=0, loudness=None, true_peak=None, eq=None, compress=None):
+                      initial_suppression_steps=0, loudness=None, true_peak=None, eq=None, compress=None, ambience=None):
         """top_k / top_p / temperature / seed: one value for the call, or one per TEXT (the segments `cut_text` makes of a text
         inherit its values); see Text2SemanticDecoder.infer_batched.
 
@@ -1602,11 +1636,22 @@ class TTS:
         compress: None, a preset name or a compressor.Compressor for every text, or a list with one of those per TEXT (a wrong
         length raises ValueError).  The finished clips of the texts with one go through their compressors in ONE packed
         gsv_compressor call (compressor.py) behind the equaliser call and ahead of the loudness call, the distinct
-        parameter sets passed once, and carry `comp`, as in infer.  A text with None comes back exactly as without the parameter."""
+        parameter sets passed once, and carry `comp`, as in infer.  A text with None comes back exactly as without the parameter.
+
+        ambience: None, a preset name or a reverb.Reverb for every text, or a list with one of those per TEXT (a wrong length
+        raises ValueError).  The finished clips of the texts with one go through their reverbs in ONE packed gsv_reverb call
+        (reverb.py) behind the compressor call and ahead of the loudness call, the distinct parameter sets passed
+        once, and carry `ambience`, as in infer.  A text with None comes back exactly as without the parameter."""
         with self._infer_lock:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
+                if ambience is not None:
+                    if isinstance(ambience, (list, tuple)) and len(ambience) != len(texts):
+                        raise ValueError("ambience has %d entries for %d requests" % (len(ambience), len(texts)))
+                    ambience = [_check_ambience(v) for v in (ambience if isinstance(ambience, (list, tuple)) else [ambience] * len(texts))]
+                    if all(v is None for v in ambience):
+                        ambience = None
                 if compress is not None:
                     if isinstance(compress, (list, tuple)) and len(compress) != len(texts):
                         raise ValueError("compress has %d entries for %d requests" % (len(compress), len(texts)))
@@ -1825,6 +1870,13 @@ class TTS:
                     for i, a, rec in zip(pick, shaped, recs):
                         clips[i].audio_data = a
                         clips[i].comp = rec
+                if ambience is not None:    # one packed call over the texts that asked, between the compressor and the loudness call
+                    from . import reverb as rv
+                    pick = [i for i, v in enumerate(ambience) if v is not None]
+                    shaped, recs = rv.reverberate([clips[i].audio_data for i in pick], self.samplerate, [ambience[i] for i in pick], device=dev)
+                    for i, a, rec in zip(pick, shaped, recs):
+                        clips[i].audio_data = a
+                        clips[i].ambience = rec
                 if loudness is not None:    # one packed call over the texts that asked
                     from . import loudness as ld
                     held = [true_peak is not None and true_peak[i] is not None for i in range(len(clips))]

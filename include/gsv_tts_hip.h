@@ -718,6 +718,53 @@ int gsv_compressor_host(const float* x, size_t n_x, const gsv_compressor_clip* c
                         int n_params, float* out, gsv_compressor_record* records, void* work, size_t work_bytes);
 int gsv_compressor_math_host(int which, const double* in, double* out, size_t n);
 
+/* Reverb: n_clips clips of one packed fp32 buffer, each through Freeverb -- eight parallel damped comb filters, their sum through
+ * four all-pass filters in series -- with one of n_params parameter sets (csrc/reverb.h).  From zero state, in fp64,
+ * per sample, v = x[n]:
+ *   u = gin v;   comb k: o_k = b_k[n - comb[k]];  l_k = (1 - d) o_k + d l_k;  b_k[n] = u + fb l_k;
+ *   s = ((((((o_0 + o_1) + o_2) + o_3) + o_4) + o_5) + o_6) + o_7;
+ *   all-pass j in order: t = a_j[n - allpass[j]];  a_j[n] = s + 0.5 t;  s = t - s;
+ *   y = fp32(gw s + gd v), saturating at +-FLT_MAX.  The output has the clip's length: the tail behind it is cut.
+ *   params [n_params] (HOST memory in both entries): the twelve delays in samples, each 1..GSV_RVB_MAX_DELAY; d and fb in [0, 1);
+ *   gin, gw, gd finite.  Whoever makes them needs the sampling rate; this call does not.
+ *   x: fp32 [n_x]; clip c is x[offset, offset + n_samples), mono; the clips do not overlap.  params: an index into params, or -1
+ *   for a clip whose peaks are measured and whose samples are copied.
+ *   out: x (in place) or a second buffer of n_x floats; only [offset, offset + n_samples) of each clip is written.
+ *   records [n_clips]: peak_in = max |x|, peak_out = max |y| and flags: GSV_RVB_REVERBED for a clip that went through the network.
+ *   A clip holding a NaN or an infinity (GSV_RVB_NONFINITE) comes back bit for bit, peak_out = peak_in = that NaN or infinity; so
+ *   does a clip with params -1, flags 0.  An empty clip is legal.
+ *   work: caller-owned, gsv_reverb_work_bytes(clips, n_clips, params, n_params) bytes (0: bad arguments), 16-byte aligned; 72
+ *   bytes per sample of the clips that have a parameter set.
+ *   gsv_reverb: x, out, records and work are DEVICE memory, clips and params HOST memory.  One small upload (the clip rows, the
+ *   parameters, the scan's powers) and seven launches on `stream`; nothing allocated, nothing read back by the host.
+ *   gsv_reverb_host: the same over HOST memory from the same scalar routines -- the CPU path and the device's oracle (device
+ *   records and samples equal the host's bit for bit); it needs no GPU.
+ * GSV_ERR_ARG: a null pointer, a bad clip or parameter-set count (1..65535 clips, 0..65535 sets), an index outside the sets, a
+ * clip outside [0, n_x), a delay, d, fb or a gain outside the ranges above, a workspace that is too small or misaligned. */
+typedef struct {
+    int64_t offset;         /* first sample of the clip in x */
+    int32_t n_samples;
+    int32_t params;         /* index into params; -1: measure the peaks, copy */
+} gsv_reverb_clip;
+typedef struct {
+    int32_t comb[8];        /* the comb delays in samples, each 1..GSV_RVB_MAX_DELAY */
+    int32_t allpass[4];     /* the all-pass delays in samples, likewise */
+    double d, fb;           /* damping and feedback, each in [0, 1) */
+    double gin, gw, gd;     /* input, wet and dry gains, finite */
+} gsv_reverb_params;
+typedef struct {
+    float peak_in, peak_out;
+    int32_t flags, pad;
+} gsv_reverb_record;
+#define GSV_RVB_REVERBED 1      /* the clip went through the network */
+#define GSV_RVB_NONFINITE 4     /* a NaN or an infinity among the samples */
+#define GSV_RVB_MAX_DELAY 32768
+size_t gsv_reverb_work_bytes(const gsv_reverb_clip* clips, int n_clips, const gsv_reverb_params* params, int n_params);
+int gsv_reverb(const float* x, size_t n_x, const gsv_reverb_clip* clips, int n_clips, const gsv_reverb_params* params, int n_params,
+               float* out, gsv_reverb_record* records, void* work, size_t work_bytes, void* stream);
+int gsv_reverb_host(const float* x, size_t n_x, const gsv_reverb_clip* clips, int n_clips, const gsv_reverb_params* params, int n_params,
+                    float* out, gsv_reverb_record* records, void* work, size_t work_bytes);
+
 /* Stream equaliser: the equaliser above for a stream that arrives in pushes (csrc/eqstream.h).  An equaliser is
  * causal: a push of n samples emits n samples (no delay), a flush emits nothing extra (no ring-out) and returns the state to
  * fresh, so that the next push starts a new stream with the same design.  The emitted samples, concatenated, are the bytes
