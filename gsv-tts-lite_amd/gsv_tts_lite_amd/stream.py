@@ -22,6 +22,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native as N
+from .finish import STREAM_STAGES
 
 
 def sola(prev_tail: torch.Tensor, chunk: torch.Tensor, search_len: int = 320) -> Tuple[torch.Tensor, int]:
@@ -60,19 +61,18 @@ class ChunkSplicer:
 
 
 class _Emitted:
-    """a chunk on its way to the host: ready() asks the copy's event, result() waits for it"""
+    """a chunk on its way to the host: ready() asks the copy's event, result() waits for it.  `eq`, `comp`, `level`, `limit`: the
+    record of that stage's push (eq.EqStreamRecord, compressor.CmpStreamRecord, level.LevelRecord, limiter.StreamLimiterRecord)
+    once result() has been called, None without the stage."""
 
-    def __init__(self, emitter, bufs, event, pcm_at=None, level_at=None, limit_at=None, eq_at=None, comp_at=None):
+    def __init__(self, emitter, bufs, event, at):
         self._emitter, self._bufs, self._event, self._value = emitter, bufs, event, None
-        self._comp_at = comp_at     # with a compressor: where its record starts in the buffer (fp32 elements)
-        self.comp = None            # and the record itself (compressor.CmpStreamRecord), once result() has been called
-        self._eq_at = eq_at         # with an equaliser: where its record starts in the buffer (fp32 elements)
-        self.eq = None              # and the record itself (eq.EqStreamRecord), once result() has been called
-        self._pcm_at = pcm_at       # with a track: where its record starts in the buffer (fp32 elements)
-        self._level_at = level_at   # with a leveller: where its record starts
-        self.level = None           # and the record itself (level.LevelRecord), once result() has been called
-        self._limit_at = limit_at   # with a limiter: where its record starts; its samples lie behind the record
-        self.limit = None           # and the record itself (limiter.StreamLimiterRecord), once result() has been called
+        # _eq_at, _comp_at, _level_at, _limit_at, _pcm_at: where that stage's record -- the track's for pcm -- starts in the buffer
+        # (fp32 elements), None without it; a limiter's samples lie behind its record
+        self._pcm_at = at.get("pcm")
+        for st in STREAM_STAGES:
+            setattr(self, "_%s_at" % st.handle, at.get(st.handle))
+            setattr(self, st.handle, None)
 
     def ready(self) -> bool:
         return self._value is not None or self._event.query()
@@ -86,25 +86,18 @@ class _Emitted:
             host = self._bufs[1]
             n_out, k, h, _ = host[:4].view(torch.int32).tolist()
             self._value = (host[4: 4 + n_out].numpy().copy(), k, h)
-            if self._eq_at is not None:
-                from . import eq
-                self.eq = eq.stream_record(host[self._eq_at: self._eq_at + eq.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
-            if self._comp_at is not None:
-                from . import compressor
-                at = self._comp_at
-                self.comp = compressor.stream_record(host[at: at + compressor.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
-            if self._level_at is not None:
-                from . import level
-                self.level = level.record(host[self._level_at: self._level_at + level.RECORD_BYTES // 4].numpy().view("uint8"))
-            if self._limit_at is not None:
-                from . import limiter
-                at = self._limit_at
-                self.limit = limiter.stream_record(host[at: at + limiter.STREAM_RECORD_BYTES // 4].numpy().view("uint8"))
-                self._value = (host[at + 8: at + 8 + self.limit.emitted].numpy().copy(), k, h)
+            for st in STREAM_STAGES:
+                at = getattr(self, "_%s_at" % st.handle)
+                if at is None:
+                    continue
+                rec = st.record(host[at: at + st.words].numpy().view("uint8"))
+                setattr(self, st.handle, rec)
+                if not st.in_place:
+                    self._value = (host[at + st.words: at + st.words + rec.emitted].numpy().copy(), k, h)
             if self._pcm_at is not None:
-                fmt = self._emitter.track.fmt
-                packets = int(host[self._pcm_at: self._pcm_at + 4].view(torch.int32)[0])
-                pcm = host[self._pcm_at + 4:].view(torch.int16)[: packets * fmt.packet * fmt.channels]
+                at, fmt = self._pcm_at, self._emitter.track.fmt
+                packets = int(host[at: at + 4].view(torch.int32)[0])
+                pcm = host[at + 4:].view(torch.int16)[: packets * fmt.packet * fmt.channels]
                 self._value += (pcm.numpy().copy().reshape(packets, fmt.packet * fmt.channels),)
             self._emitter._free.append(self._bufs)
             self._bufs = None
@@ -146,7 +139,10 @@ class ChunkEmitter:
     on the same samples, their number read on the device from the record of the stage in front; the stages behind read their
     length from the compressor's record, which rides 8-byte aligned in the same buffer and the same copy, and the handle carries
     it in `comp`.  Its state spans the text like the others', and `flush` ends its stream too.  Without one the buffer's layout
-    and every byte are what they were."""
+    and every byte are what they were.
+
+    Which stages there are, their order, their records' sizes and who reads whose length is finish.STREAM_STAGES:
+    push() and the handle's result() walk that table."""
 
     def __init__(self, overlap_samples: int, search_len: int = 320, track=None, level=None, limit=None, eq=None, compress=None):
         self.overlap, self.search_len, self.track, self.level, self.limit = int(overlap_samples), int(search_len), track, level, limit
@@ -176,45 +172,37 @@ class ChunkEmitter:
         prev = None if self._cur is None else self._tails[self._cur]
         nxt = 0 if self._cur is None else self._cur ^ 1
         used = 4 + n + int(mute_samples)
-        lim_cap = 0 if self.limit is None else self.limit.capacity(used - 4)     # the most samples the limiter emits
-        pcm_cap = 0 if self.track is None else (self.track.capacity(lim_cap or used - 4) + 1) // 2      # int16 pairs as fp32 elements
-        erec = 0 if self.eq is None else (used & 1) + 8           # the equaliser's record, 8-byte aligned, as fp32 elements
-        crec = 0 if self.compress is None else ((used + erec) & 1) + 10   # the compressor's record, 8-byte aligned
-        lrec = 0 if self.level is None else ((used + erec + crec) & 1) + 10       # the level record, 8-byte aligned
-        mrec = 0 if self.limit is None else ((used + erec + crec + lrec) & 1) + 8 + lim_cap    # the limiter's record, 8-byte aligned, and its samples
-        dbuf, hbuf = bufs = self._buffers(used + erec + crec + lrec + mrec + (0 if self.track is None else 4 + pcm_cap), dev)
+        # [rec 4 | samples | a stage's record, 8-byte aligned (| its samples, when it does not run in place) | ... | track rec 4 |
+        # packets], all in fp32 elements, in the chain's order (finish.STREAM_STAGES)
+        layout, cap = [], used - 4          # cap: the most samples the next stage reads
+        for st in STREAM_STAGES:
+            stage = getattr(self, st.emitter)
+            if stage is not None:
+                used += used & 1
+                layout.append((st, stage, used, cap))
+                cap = cap if st.in_place else stage.capacity(cap)
+                used += st.words + (0 if st.in_place else cap)
+        pcm_cap = 0 if self.track is None else (self.track.capacity(cap) + 1) // 2      # int16 pairs as fp32 elements
+        dbuf, hbuf = bufs = self._buffers(used + (0 if self.track is None else 4 + pcm_cap), dev)
+        base = dbuf.data_ptr()
         N.check(L.gsv_stream_emit(None if prev is None else prev.data_ptr(), x.data_ptr(), n, self.overlap, self.search_len,
-                                  int(bool(is_final)), int(bool(trim_head)), int(mute_samples), dbuf[4:].data_ptr(),
-                                  self._tails[nxt].data_ptr(), dbuf.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                  int(bool(is_final)), int(bool(trim_head)), int(mute_samples), base + 16,
+                                  self._tails[nxt].data_ptr(), base, self._ws.data_ptr(), self._ws.numel(),
                                   N.current_stream_ptr(dev)))
         self._cur = nxt
-        pcm_at, level_at, limit_at, eq_at, comp_at, n_samples = None, None, None, None, None, used - 4
-        src, src_cap, src_len = dbuf[4:].data_ptr(), n_samples, dbuf.data_ptr()       # what the next stage reads: samples, capacity, length
-        if self.eq is not None:          # [rec 4 | samples | eq rec 8 (8-byte aligned) | ...]: in place, first of all
-            eq_at = used + (used & 1)
-            self.eq.enqueue(src, n_samples, src_len, flush, src, dbuf[eq_at:].data_ptr())
-            src_len = dbuf[eq_at:].data_ptr()
-            used += erec
-        if self.compress is not None:    # [... | compressor rec 10 (8-byte aligned) | ...]: in place, behind the equaliser
-            comp_at = used + (used & 1)
-            self.compress.enqueue(src, n_samples, src_len, flush, src, dbuf[comp_at:].data_ptr())
-            src_len = dbuf[comp_at:].data_ptr()
-            used += crec
-        if self.level is not None:       # [rec 4 | samples | level rec 10 (8-byte aligned) | ...]: in place, before the track reads them
-            level_at = used + (used & 1)
-            self.level.enqueue(dbuf[4:].data_ptr(), n_samples, src_len, flush, dbuf[4:].data_ptr(), dbuf[level_at:].data_ptr())
-            used += lrec
-        if self.limit is not None:       # [... | limiter rec 8 (8-byte aligned) | its samples n + delay | ...]: out of place
-            limit_at = used + (used & 1)
-            self.limit.enqueue(dbuf[4:].data_ptr(), n_samples, src_len, flush, dbuf[limit_at + 8:].data_ptr(),
-                               dbuf[limit_at:].data_ptr())
-            src, src_cap, src_len = dbuf[limit_at + 8:].data_ptr(), lim_cap, dbuf[limit_at:].data_ptr()
-            used += mrec
-        if self.track is not None:       # [rec 4 | samples | track rec 4 | packets], all in fp32 elements
-            pcm_at = used
-            self.track.enqueue(src, src_cap, src_len, flush, dbuf[used + 4:].data_ptr(), dbuf[used:].data_ptr())
+        at, src, src_len = {}, base + 16, base          # what the next stage reads: the samples, and their number on the device
+        for st, stage, rec_at, src_cap in layout:
+            at[st.handle] = rec_at
+            out = src if st.in_place else base + 4 * (rec_at + st.words)
+            stage.enqueue(src, src_cap, src_len, flush, out, base + 4 * rec_at)
+            src = out
+            if st.gives_length:
+                src_len = base + 4 * rec_at
+        if self.track is not None:
+            at["pcm"] = used
+            self.track.enqueue(src, cap, src_len, flush, base + 4 * (used + 4), base + 4 * used)
             used += 4 + pcm_cap
         hbuf[:used].copy_(dbuf[:used], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        return _Emitted(self, bufs, ev, pcm_at, level_at, limit_at, eq_at, comp_at)
+        return _Emitted(self, bufs, ev, at)

@@ -44,7 +44,6 @@ gsv_align_viterbi, replacing TTS.py:1744-1797) and the word-timing / text-span b
 from __future__ import annotations
 
 import logging
-import math
 import numbers
 import os
 import re
@@ -54,12 +53,13 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import slot_sampling
+from . import finish, slot_sampling
+from .finish import _check_loudness_seed, _check_true_peak  # noqa: F401  (the names tests and callers import from here)
 from ._native import VOC_MAX_SEGMENTS
 from . import subtitles as sub
 from .batchmath import balance_order, per_text_values, split_bounds
 from .stream import ChunkEmitter, ChunkSplicer
-from .track import TrackFormat, TrackResampler
+from .track import TrackFormat
 from .loader import Gpt, Sovits, convert_to_safetensors, get_gpt_weights, get_sovits_weights
 
 log = logging.getLogger("gsv_tts_lite_amd")
@@ -156,9 +156,7 @@ class AudioClip:
         lufs / gain / limited say what was measured and done (loudness.normalise)"""
         from . import loudness
         audio, rec = loudness.normalise(self.audio_data, self.samplerate, target, peak_limit)
-        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp, out.ambience = self.eq, self.comp, self.ambience
-        return _with_loudness(out, rec)
+        return finish.with_records(self._derived(audio, "eq", "comp", "ambience"), {"loudness": rec})
 
     def equalised(self, eq="voice") -> "AudioClip":
         """a new clip through the equaliser `eq` -- an eq.EQ or a preset name (eq.py) --, same subtitles and text; its
@@ -167,9 +165,7 @@ class AudioClip:
         if not isinstance(eq, (str, eqm.EQ)):
             raise ValueError("eq: a preset name (%s) or an eq.EQ, not %r" % (", ".join(eqm.PRESETS), type(eq).__name__))
         audio, rec = eqm.equalise(self.audio_data, self.samplerate, eq)
-        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp, out.ambience = rec, self.comp, self.ambience
-        return out
+        return finish.with_records(self._derived(audio, "comp", "ambience"), {"eq": rec})
 
     def compressed(self, c="voice") -> "AudioClip":
         """a new clip through the compressor `c` -- a compressor.Compressor or a preset name (compressor.py) --, same
@@ -179,9 +175,7 @@ class AudioClip:
         if not isinstance(c, (str, cm.Compressor)):
             raise ValueError("compress: a preset name (%s) or a compressor.Compressor, not %r" % (", ".join(cm.PRESETS), type(c).__name__))
         audio, rec = cm.compress(self.audio_data, self.samplerate, c)
-        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp, out.ambience = self.eq, rec, self.ambience
-        return out
+        return finish.with_records(self._derived(audio, "eq", "ambience"), {"compress": rec})
 
     def ambient(self, r="voice") -> "AudioClip":
         """a new clip through the reverb `r` -- a reverb.Reverb or a preset name (reverb.py) --, same subtitles, text
@@ -191,9 +185,7 @@ class AudioClip:
         if not isinstance(r, (str, rv.Reverb)):
             raise ValueError("ambience: a preset name (%s) or a reverb.Reverb, not %r" % (", ".join(rv.PRESETS), type(r).__name__))
         audio, rec = rv.reverberate(self.audio_data, self.samplerate, r)
-        out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.eq, out.comp, out.ambience = self.eq, self.comp, rec
-        return out
+        return finish.with_records(self._derived(audio, "eq", "comp"), {"ambience": rec})
 
     def true_peak(self) -> float:
         """the true peak of audio_data in dBTP (limiter.true_peak: the largest magnitude of the clip oversampled 4x, measured on
@@ -206,9 +198,14 @@ class AudioClip:
         dbtp / limited say what came out and whether the limiter acted, lufs / gain are kept"""
         from . import limiter
         audio, rec = limiter.limit(self.audio_data, self.samplerate, ceiling_db)
+        return finish.with_records(self._derived(audio, "lufs", "gain", "eq", "comp", "ambience"), {"true_peak": rec})
+
+    def _derived(self, audio, *keep):
+        """a clip like this one -- same subtitles and text -- with new samples; of the stages' records it keeps the fields named"""
         out = AudioClip(self.audio_queue, audio, self.samplerate, self.audio_len_s, self.subtitles, self.orig_text)
-        out.lufs, out.gain, out.eq, out.comp, out.ambience = self.lufs, self.gain, self.eq, self.comp, self.ambience
-        return _with_true_peak(out, rec)
+        for field in keep:
+            setattr(out, field, getattr(self, field))
+        return out
 
     def _save_wav(self, save_path):
         import wave
@@ -216,85 +213,6 @@ class AudioClip:
         with wave.open(save_path, "wb") as w:
             w.setnchannels(1); w.setsampwidth(2); w.setframerate(self.samplerate)
             w.writeframes(pcm.tobytes())
-
-
-def _with_loudness(clip, rec):
-    clip.lufs, clip.gain, clip.limited = rec.lufs, rec.gain, rec.limited
-    return clip
-
-
-def _with_records(clip, rec, lim, eqr=None, comp=None, amb=None):
-    """a clip of infer / infer_vc with loudness= (rec), true_peak= (lim), eq= (eqr), compress= (comp), ambience= (amb) or several
-    of them"""
-    clip.eq, clip.comp, clip.ambience = eqr, comp, amb
-    if rec is not None:
-        _with_loudness(clip, rec)
-    return clip if lim is None else _with_true_peak(clip, lim)
-
-
-def _with_true_peak(clip, rec):
-    clip.dbtp, clip.limited = rec.dbtp_out, rec.limited
-    return clip
-
-
-def _check_true_peak(v):
-    from . import limiter
-    return limiter.check_ceiling(v)
-
-
-def _check_eq(v, rate):
-    """an eq= value: None, a preset name or an eq.EQ -> None (also for an EQ that is the identity) or the EQ"""
-    if v is None:
-        return None
-    from . import eq
-    return eq.resolve(v, rate)
-
-
-def _check_compress(v):
-    """a compress= value: None, a preset name or a compressor.Compressor -> None (also for the identity) or the Compressor"""
-    if v is None:
-        return None
-    from . import compressor
-    return compressor.resolve(v)
-
-
-def _check_ambience(v):
-    """an ambience= value: None, a preset name or a reverb.Reverb -> None (also for the identity) or the Reverb"""
-    if v is None:
-        return None
-    from . import reverb
-    return reverb.resolve(v)
-
-
-def _with_level(clip, rec):
-    """a clip of a levelled stream: the running measure of the UNLEVELLED stream at its end, the gain of its last sample, and
-    whether any sample of the stream so far was set to the peak limit"""
-    clip.lufs, clip.gain, clip.limited = rec.lufs, rec.gain_last, rec.limited
-    return clip
-
-
-def _with_stream_limit(clip, rec):
-    """a clip of a stream held under a ceiling (limiter.StreamLimiterRecord): whether the limiter has acted on the stream so far, the
-    highest true peak of the unlimited stream so far, the smallest gain among the clip's samples.  No `dbtp`: the output's true
-    peak is not measured"""
-    clip.limited, clip.dbtp_in, clip.gain_min = rec.limited_ever, rec.dbtp_in, rec.min_gain
-    return clip
-
-
-def _check_loudness(v):
-    if v is not None and not np.isfinite(float(v)):
-        raise ValueError("loudness target %r" % (v,))
-    return None if v is None else float(v)
-
-
-def _check_loudness_seed(v):
-    """a stream's loudness_seed: None, or the last `lufs` of the same voice -- which is -inf when nothing was measured, and then
-    there is no seed either"""
-    if v is None or float(v) == -np.inf:
-        return None
-    if not np.isfinite(float(v)):
-        raise ValueError("loudness seed %r" % (v,))
-    return float(v)
 
 
 def cut_text(text: str, minlen: int = 10) -> list:
@@ -345,21 +263,14 @@ class _TextLine:
     """One text of TTS.infer_stream_batched: the vocoder side of its stream, strictly sequential -- what TTS.infer_stream keeps in
     local variables and in `vq.enc_p.y_overlap`, per text."""
 
-    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, track=None, level=None, limit=None, eq=None,
-                 compress=None):
+    def __init__(self, text, cuts, ge, overlap_samples, speed, noise_scale, cut_mute, generator, chain):
         self.text, self.cuts, self.ge, self.speed, self.noise_scale = text, cuts, ge, speed, noise_scale
         self.cut_mute, self.generator = cut_mute, generator
         self.segs = []                              # per segment: (phoneme ids [1, P] on the device, word2ph, norm_text)
         self.waiting = [[] for _ in cuts]           # per segment: (cumulative tokens, is_final) not decoded yet
         self.in_flight = []                         # (ChunkEmitter handle, frame -> phoneme path in pinned host memory or None, is_final, first of its segment)
-        # the text's own TrackResampler / StreamLeveller / StreamLimiter / StreamEQ / StreamCompressor, or None (without a limiter,
-        # an equaliser or a compressor: the call as it always was)
-        stages = {} if limit is None else {"limit": limit}
-        if eq is not None:
-            stages["eq"] = eq
-        if compress is not None:
-            stages["compress"] = compress
-        self.emitter = ChunkEmitter(overlap_samples, track=track, level=level, **stages)
+        self.chain = chain                          # the text's own finish.StreamChain: its stages' states and its track's
+        self.emitter = ChunkEmitter(overlap_samples, **chain.emitter_keywords())
         self.seg, self.final_issued = 0, False      # the segment being vocoded; its final chunk is in flight
         self.y_overlap, self.valid_start_idx, self.chunk_idx, self.last_subtitles_end, self.head_offset = None, 0, 0, 0, 0
         self.cur_text_l, self.last_end_s, self.audio_len_s = 0, 0, 0.0
@@ -970,8 +881,7 @@ class TTS:
         by the look-ahead limiter on the device (limiter.py) and carries dbtp (its true peak behind the limiter) and
         limited (the limiter acted).  With loudness= as well the gain to the target is applied whatever the peak becomes, and the
         limiter then holds the ceiling: the loudness that comes out is what the limiter leaves."""
-        loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
-        compress, ambience = _check_compress(compress), _check_ambience(ambience)
+        chain = finish.resolve(self.samplerate, eq=eq, compress=compress, ambience=ambience, loudness=loudness, true_peak=true_peak)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -1007,10 +917,10 @@ class TTS:
                 if subtitles:
                     sub.increment_subtitle_times(subtitles, -head_offset / self.samplerate)
                     subtitles[0]["start_s"] = max(0, subtitles[0]["start_s"])
-                if loudness is not None or true_peak is not None or eq is not None or compress is not None or ambience is not None:
-                    audio, rec, lim, eqr, comp, amb = self._finish_on_device(audio.float(), loudness, true_peak, eq, compress, ambience)
-                    return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles, text),
-                                         rec, lim, eqr, comp, amb)
+                if finish.asked(chain):
+                    audio, recs = finish.finish_clip(audio.float(), chain, self.samplerate)
+                    return finish.with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
+                                                         text), recs)
                 audio = audio.float().cpu().numpy()
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
@@ -1020,62 +930,13 @@ class TTS:
             finally:
                 self._empty_cache()
 
-    def _finish_on_device(self, audio, target, ceiling=None, eq=None, compress=None, ambience=None):
-        """the tail of infer / infer_vc with eq=, compress=, ambience=, loudness= or true_peak=: the peak rule (an IEEE division by max(peak, 1):
-        dividing by 1 is exact, so the same bits as the host's `if peak > 1` without reading the peak back), the 0.2 s of zeros, then
-        one gsv_eq call (eq), one gsv_compressor call (compress), one gsv_reverb call (ambience), one gsv_loudness call (target) and
-        one gsv_limiter call (ceiling) over the finished clip in place -- the order of the reference's chain --, their records
-        written behind the samples: ONE download carries all -> (numpy samples, loudness record or None, limiter record or None,
-        eq record or None, compressor record or None, reverb record or None).  Ahead of the limiter the gain to the target is applied with no peak limit: the limiter holds the
-        ceiling."""
-        from . import compressor as cm
-        from . import eq as eqm
-        from . import limiter as lm
-        from . import loudness as ld
-        from . import reverb as rv
-        if audio.numel():
-            audio = audio / audio.abs().max().clamp(min=1)
-        n = audio.numel() + int(0.2 * self.samplerate)
-        words = (ld.RECORD_BYTES // 4 if target is not None else 0) + (lm.RECORD_BYTES // 4 if ceiling is not None else 0)
-        eq_words = eqm.RECORD_BYTES // 4 if eq is not None else 0              # in front of the other two: 16 bytes keep their alignment
-        cm_words = cm.RECORD_BYTES // 4 if compress is not None else 0         # and so do these 16
-        rv_words = rv.RECORD_BYTES // 4 if ambience is not None else 0         # and these
-        words += eq_words + cm_words + rv_words
-        tail = (n + 1) // 2 * 2 - audio.numel() + words                        # zeros to n, to an 8-byte boundary, the records
-        buf = torch.cat([audio, torch.zeros(tail, dtype=audio.dtype, device=audio.device)])
-        at = buf.numel() - words
-        if eq is not None:
-            eqm.run_packed(buf[:n], [0], [n], [0], [eqm.design(eq, self.samplerate)], buf[:n], buf[at: at + eq_words].view(torch.uint8))
-        eqr_at, at = at, at + eq_words
-        if compress is not None:
-            cm.run_packed(buf[:n], [0], [n], [0], [compress.coefficients(self.samplerate)], buf[:n], buf[at: at + cm_words].view(torch.uint8))
-        cmr_at, at = at, at + cm_words
-        if ambience is not None:
-            rv.run_packed(buf[:n], [0], [n], [0], [ambience.parameters(self.samplerate)], buf[:n], buf[at: at + rv_words].view(torch.uint8))
-        rvr_at, at = at, at + rv_words
-        if target is not None:
-            ld.run_packed(buf[:n], [0], [n], [target], self.samplerate, 1.0 if ceiling is None else math.inf, buf[:n],
-                          buf[at: at + ld.RECORD_BYTES // 4].view(torch.uint8))
-        if ceiling is not None:
-            L, R = lm.times(self.samplerate)
-            lm.run_packed(buf[:n], [0], [n], [ceiling], L, R, buf[:n], buf[buf.numel() - lm.RECORD_BYTES // 4:].view(torch.uint8))
-        host = buf.cpu().numpy()
-        rec = ld.records(host[at: at + ld.RECORD_BYTES // 4].view(np.uint8))[0] if target is not None else None
-        lim = lm.records(host[host.size - lm.RECORD_BYTES // 4:].view(np.uint8))[0] if ceiling is not None else None
-        eqr = eqm.records(host[eqr_at: eqr_at + eq_words].view(np.uint8))[0] if eq is not None else None
-        comp = cm.records(host[cmr_at: cmr_at + cm_words].view(np.uint8))[0] if compress is not None else None
-        amb = rv.records(host[rvr_at: rvr_at + rv_words].view(np.uint8))[0] if ambience is not None else None
-        return host[:n], rec, lim, eqr, comp, amb
-
     @torch.inference_mode()
     def infer_vc(self, spk_audio_path, prompt_audio_path, prompt_audio_text, noise_scale=0.5, speed=1.0, sovits_model=None,
                  loudness=None, true_peak=None, eq=None, compress=None, ambience=None):
         """TTS.py:871-964, voice conversion: the prompt's own semantic tokens and phonemes go straight to the SoVITS
         decoder with the target speaker's `ge`; word timings always come back (the reference aligns unconditionally here).
         loudness, true_peak, eq, compress, ambience: as in infer."""
-        loudness, true_peak, eq = _check_loudness(loudness), _check_true_peak(true_peak), _check_eq(eq, self.samplerate)
-        compress, ambience = _check_compress(compress), _check_ambience(ambience)
-        finish = loudness is not None or true_peak is not None or eq is not None or compress is not None or ambience is not None
+        chain = finish.resolve(self.samplerate, eq=eq, compress=compress, ambience=ambience, loudness=loudness, true_peak=true_peak)
         with self._infer_lock:
             try:
                 if not self._check_pause(prompt_audio_text):
@@ -1092,16 +953,16 @@ class TTS:
                 phones, word2ph, _, norm_text = self._phones_and_bert(prompt_audio_text)
                 audio, attn = vq.decode(prompt.unsqueeze(0), torch.tensor(phones, dtype=torch.int64, device=dev).unsqueeze(0), ge,
                                         noise_scale=noise_scale, speed=speed)
-                if finish:
-                    audio, rec, lim, eqr, comp, amb = self._finish_on_device(audio[0, 0, :].float(), loudness, true_peak, eq, compress, ambience)
+                if finish.asked(chain):
+                    audio, recs = finish.finish_clip(audio[0, 0, :].float(), chain, self.samplerate)
                 else:
                     audio = audio[0, 0, :].float().cpu().numpy()
                 subtitles = sub.get_subtitles(word2ph, sub.viterbi_monotonic(attn), speed, sovits_hz=self.sovits_hz)
                 self._close_subtitles(subtitles, word2ph, 0.2)
                 subtitles = sub.sub2text_index(subtitles, norm_text, prompt_audio_text)
-                if finish:
-                    return _with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
-                                                   prompt_audio_text), rec, lim, eqr, comp, amb)
+                if finish.asked(chain):
+                    return finish.with_records(AudioClip(self.audio_queue, audio, self.samplerate, len(audio) / self.samplerate, subtitles,
+                                                         prompt_audio_text), recs)
                 peak = np.abs(audio).max() if audio.size else 0.0
                 if peak > 1:
                     audio = audio / peak
@@ -1206,9 +1067,7 @@ class TTS:
         delay, the clips keep their lengths.  Each clip carries `comp`, the compressor.CmpStreamRecord: the peaks before and after
         and the smallest gain of its samples and of the stream so far, and `total`, the stream's samples so far.  A compressor
         that is the identity is as none."""
-        loudness, loudness_seed, true_peak = _check_loudness(loudness), _check_loudness_seed(loudness_seed), _check_true_peak(true_peak)
-        eq = _check_eq(eq, self.samplerate)
-        compress = _check_compress(compress)
+        chain = finish.resolve(self.samplerate, eq=eq, compress=compress, loudness=loudness, loudness_seed=loudness_seed, true_peak=true_peak)
         with self._infer_lock:
             try:
                 if self._contains_chinese(text):
@@ -1234,11 +1093,7 @@ class TTS:
                 overlap_samples = overlap_len * vq.samples_per_frame
                 audio_len_s, cur_text_l, last_end_s = 0.0, 0, 0
                 cuts = cut_text(text, cut_minlen)
-                resampler = None if track is None else TrackResampler(track, self.samplerate, dev)
-                leveller = None if loudness is None else self._leveller(loudness, loudness_seed, dev, true_peak is not None)
-                limiter = None if true_peak is None else self._limiter(true_peak, dev)
-                equaliser = None if eq is None else self._equaliser(eq, dev)
-                squeezer = None if compress is None else self._stream_compressor(compress, dev)
+                stages = finish.StreamChain(chain, self.samplerate, dev, track)
                 for i, text_cut in enumerate(cuts):
                     phones2, word2ph, bert2, norm_text = self._phones_and_bert(text_cut)
                     ids = torch.tensor(phones1 + phones2, dtype=torch.int64, device=dev).unsqueeze(0)
@@ -1285,29 +1140,10 @@ class TTS:
                                 last_subtitles_end = len(subtitles) - 1
                                 if not is_final and new_subtitles:
                                     new_subtitles[-1]["end_s"] = None
-                            if equaliser is not None:
-                                audio = equaliser.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
-                            if squeezer is not None:
-                                audio = squeezer.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
-                            if leveller is not None:
-                                audio = leveller.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
-                            if limiter is not None:
-                                audio = limiter.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
-                            pcm = None if resampler is None else resampler.push(audio, flush=is_final and i == len(cuts) - 1)
+                            audio = stages.push_tensor(audio, flush=is_final and i == len(cuts) - 1)
                             audio = audio.float().cpu().numpy()
                         audio_len_s += len(audio) / self.samplerate
-                        clip = AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text)
-                        if equaliser is not None:
-                            clip.eq = equaliser.rec
-                        if squeezer is not None:
-                            clip.comp = squeezer.rec
-                        if leveller is not None:
-                            _with_level(clip, leveller.rec)
-                        if limiter is not None:
-                            _with_stream_limit(clip, limiter.rec)
-                        if resampler is not None:
-                            clip.pcm, clip.pcm_rate = pcm, track.rate
-                        yield clip
+                        yield stages.attach(AudioClip(self.audio_queue, audio, self.samplerate, audio_len_s, new_subtitles, text))
                         chunk_idx += 1
                     vq.enc_p.y_overlap = None
                     cur_text_l += len(text_cut)
@@ -1317,25 +1153,6 @@ class TTS:
                 except Exception:
                     pass
                 self._empty_cache()
-
-    def _leveller(self, target, seed, dev, held=False):
-        """held: a stream limiter follows and holds the ceiling, so the leveller's own peak limit is off (the clip path's rule)"""
-        from .level import StreamLeveller
-        if held:
-            return StreamLeveller(target, self.samplerate, dev, seed=seed, peak_limit=float("inf"))
-        return StreamLeveller(target, self.samplerate, dev, seed=seed)
-
-    def _limiter(self, ceiling, dev):
-        from .limiter import StreamLimiter
-        return StreamLimiter(ceiling, self.samplerate, dev)
-
-    def _equaliser(self, eq, dev):
-        from .eq import StreamEQ
-        return StreamEQ(eq, self.samplerate, dev)
-
-    def _stream_compressor(self, c, dev):
-        from .compressor import StreamCompressor
-        return StreamCompressor(c, self.samplerate, dev)
 
     def infer_stream_batched(self, spk_audio_paths, prompt_audio_paths, prompt_audio_texts, texts, return_subtitles=False,
                              is_cut_text=True, cut_minlen=10, cut_mute=0.4,
@@ -1392,15 +1209,8 @@ class TTS:
                 n = len(texts)
                 if n == 0:
                     return
-                loudness = [_check_loudness(v) for v in slot_sampling.per_request("loudness", loudness, n)]
-                loudness_seed = [_check_loudness_seed(v) for v in slot_sampling.per_request("loudness_seed", loudness_seed, n)]
-                true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, n)]
-                if isinstance(eq, (list, tuple)) and len(eq) != n:
-                    raise ValueError("eq has %d entries for %d requests" % (len(eq), n))
-                eq = [_check_eq(v, self.samplerate) for v in (eq if isinstance(eq, (list, tuple)) else [eq] * n)]
-                if isinstance(compress, (list, tuple)) and len(compress) != n:
-                    raise ValueError("compress has %d entries for %d requests" % (len(compress), n))
-                compress = [_check_compress(v) for v in (compress if isinstance(compress, (list, tuple)) else [compress] * n)]
+                chains = finish.resolve(self.samplerate, n, eq=eq, compress=compress, loudness=loudness, loudness_seed=loudness_seed,
+                                        true_peak=true_peak)
                 speed = slot_sampling.per_request("speed", speed, n)
                 noise_scale = slot_sampling.per_request("noise_scale", noise_scale, n)
                 if not all(s > 0 for s in speed):
@@ -1433,12 +1243,7 @@ class TTS:
                     gen_t = None if seeds[t] is None else torch.Generator().manual_seed(int(seeds[t]))
                     lines.append(_TextLine(text, cut_text(text, cut_minlen), self._ge_for(spk_audio_paths[t], sovits_model),
                                            overlap_len * vq.samples_per_frame, speed[t], noise_scale[t], cut_mute / speed[t], gen_t,
-                                           None if track is None else TrackResampler(track, self.samplerate, dev),
-                                           None if loudness[t] is None else
-                                           self._leveller(loudness[t], loudness_seed[t], dev, true_peak[t] is not None),
-                                           None if true_peak[t] is None else self._limiter(true_peak[t], dev),
-                                           None if eq[t] is None else self._equaliser(eq[t], dev),
-                                           None if compress[t] is None else self._stream_compressor(compress[t], dev)))
+                                           finish.StreamChain(finish.chain_of(chains, t), self.samplerate, dev, track)))
                 # the queue: segment 0 of every text, then segment 1, ...
                 req = [(t, j) for j in range(max(len(ln.cuts) for ln in lines)) for t, ln in enumerate(lines) if j < len(ln.cuts)]
                 seg2orig = [t for t, _ in req]
@@ -1529,7 +1334,7 @@ class TTS:
         samples -- subtitles, audio_len_s -- with the head offset the device chose.  `assign` is on the host by then (its copy was
         queued before the samples'), so nothing here reads the device"""
         handle, assign, is_final, first = ln.in_flight.pop(0)
-        audio, _, head, *pcm = handle.result()
+        audio, _, head = handle.result()[:3]
         if first:
             ln.head_offset = head
         text_cut = ln.cuts[ln.seg]
@@ -1556,18 +1361,7 @@ class TTS:
             ln.cur_text_l += len(text_cut)
             ln.seg, ln.y_overlap, ln.valid_start_idx, ln.chunk_idx, ln.last_subtitles_end = ln.seg + 1, None, 0, 0, 0
             ln.final_issued = False
-        clip = AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text)
-        if handle.eq is not None:
-            clip.eq = handle.eq
-        if handle.comp is not None:
-            clip.comp = handle.comp
-        if handle.level is not None:
-            _with_level(clip, handle.level)
-        if handle.limit is not None:
-            _with_stream_limit(clip, handle.limit)
-        if pcm:
-            clip.pcm, clip.pcm_rate = pcm[0], ln.emitter.track.fmt.rate
-        return clip
+        return ln.chain.attach(AudioClip(self.audio_queue, audio, self.samplerate, ln.audio_len_s, new_subtitles, ln.text), handle)
 
     async def infer_stream_batched_async(self, *args, executor=None, **kwargs):
         """async generator of (text index, AudioClip): infer_stream_batched in an executor thread, handed over a queue"""
@@ -1646,33 +1440,8 @@ class TTS:
             try:
                 if isinstance(texts, str):
                     texts = [texts]
-                if ambience is not None:
-                    if isinstance(ambience, (list, tuple)) and len(ambience) != len(texts):
-                        raise ValueError("ambience has %d entries for %d requests" % (len(ambience), len(texts)))
-                    ambience = [_check_ambience(v) for v in (ambience if isinstance(ambience, (list, tuple)) else [ambience] * len(texts))]
-                    if all(v is None for v in ambience):
-                        ambience = None
-                if compress is not None:
-                    if isinstance(compress, (list, tuple)) and len(compress) != len(texts):
-                        raise ValueError("compress has %d entries for %d requests" % (len(compress), len(texts)))
-                    compress = [_check_compress(v) for v in (compress if isinstance(compress, (list, tuple)) else [compress] * len(texts))]
-                    if all(v is None for v in compress):
-                        compress = None
-                if loudness is not None:
-                    loudness = [_check_loudness(v) for v in (slot_sampling.per_request("loudness", loudness, len(texts))
-                                                             if slot_sampling.is_sequence(loudness) else [loudness] * len(texts))]
-                    if all(v is None for v in loudness):
-                        loudness = None
-                if true_peak is not None:
-                    true_peak = [_check_true_peak(v) for v in slot_sampling.per_request("true_peak", true_peak, len(texts))]
-                    if all(v is None for v in true_peak):
-                        true_peak = None
-                if eq is not None:
-                    if isinstance(eq, (list, tuple)) and len(eq) != len(texts):
-                        raise ValueError("eq has %d entries for %d requests" % (len(eq), len(texts)))
-                    eq = [_check_eq(v, self.samplerate) for v in (eq if isinstance(eq, (list, tuple)) else [eq] * len(texts))]
-                    if all(v is None for v in eq):
-                        eq = None
+                chains = finish.resolve(self.samplerate, len(texts), eq=eq, compress=compress, ambience=ambience, loudness=loudness,
+                                        true_peak=true_peak)
                 segmented = slot_sampling.is_sequence(speed) or slot_sampling.is_sequence(noise_scale)
                 if segmented:   # one value per text: the lengths are checked before any device work
                     speed = slot_sampling.per_request("speed", speed, len(texts))
@@ -1856,46 +1625,7 @@ class TTS:
                     a = np.concatenate(parts) if parts else np.zeros(0, np.float32)
                     subtitles = sub.cat_subtitles(*sparts) if return_subtitles else []
                     clips.append(AudioClip(self.audio_queue, a, self.samplerate, len(a) / self.samplerate, subtitles, t))
-                if eq is not None:          # one packed call over the texts that asked, ahead of the loudness call
-                    from . import eq as eqm
-                    pick = [i for i, v in enumerate(eq) if v is not None]
-                    shaped, recs = eqm.equalise([clips[i].audio_data for i in pick], self.samplerate, [eq[i] for i in pick], device=dev)
-                    for i, a, rec in zip(pick, shaped, recs):
-                        clips[i].audio_data = a
-                        clips[i].eq = rec
-                if compress is not None:    # one packed call over the texts that asked, between the equaliser and the loudness call
-                    from . import compressor as cm
-                    pick = [i for i, v in enumerate(compress) if v is not None]
-                    shaped, recs = cm.compress([clips[i].audio_data for i in pick], self.samplerate, [compress[i] for i in pick], device=dev)
-                    for i, a, rec in zip(pick, shaped, recs):
-                        clips[i].audio_data = a
-                        clips[i].comp = rec
-                if ambience is not None:    # one packed call over the texts that asked, between the compressor and the loudness call
-                    from . import reverb as rv
-                    pick = [i for i, v in enumerate(ambience) if v is not None]
-                    shaped, recs = rv.reverberate([clips[i].audio_data for i in pick], self.samplerate, [ambience[i] for i in pick], device=dev)
-                    for i, a, rec in zip(pick, shaped, recs):
-                        clips[i].audio_data = a
-                        clips[i].ambience = rec
-                if loudness is not None:    # one packed call over the texts that asked
-                    from . import loudness as ld
-                    held = [true_peak is not None and true_peak[i] is not None for i in range(len(clips))]
-                    for limit, hold in ((1.0, False), (math.inf, True)):        # ahead of the limiter no peak limit binds
-                        pick = [i for i, v in enumerate(loudness) if v is not None and held[i] == hold]
-                        if not pick:
-                            continue
-                        scaled, recs = ld.normalise([clips[i].audio_data for i in pick], self.samplerate, [loudness[i] for i in pick], limit,
-                                                    device=dev)
-                        for i, a, rec in zip(pick, scaled, recs):
-                            clips[i].audio_data = a
-                            _with_loudness(clips[i], rec)
-                if true_peak is not None:   # one packed call over the texts that asked
-                    from . import limiter as lm
-                    pick = [i for i, v in enumerate(true_peak) if v is not None]
-                    under, recs = lm.limit([clips[i].audio_data for i in pick], self.samplerate, [true_peak[i] for i in pick], device=dev)
-                    for i, a, rec in zip(pick, under, recs):
-                        clips[i].audio_data = a
-                        _with_true_peak(clips[i], rec)
+                finish.finish_clips(clips, chains, self.samplerate, dev)
                 return tuple(clips)
             finally:
                 self._empty_cache()

@@ -189,3 +189,63 @@ def test_chunk_emitter_protocol(dev):
     em.new_segment()
     again = em.push(torch.from_numpy(sm[:n_chunk].copy()).to(dev), False).result()
     assert again[1] == 0 and np.array_equal(again[0], sm[: n_chunk - ov])
+
+
+def test_chunk_emitter_with_every_subset_of_the_stages(dev):
+    """every subset of {eq, compress, level, limit}, with and without a track -- 32 emitters -- over one three-chunk segment and a
+    one-chunk second segment: each handle's samples, records and packets are the plain emitter's samples pushed through host
+    stage objects in the chain's order.  4 + n + mute is odd in the first and the last push and even in the other two, so every
+    record is placed both with and without its alignment pad."""
+    import itertools
+    from gsv_tts_lite_amd import compressor as CM
+    from gsv_tts_lite_amd import eq as EQM
+    from gsv_tts_lite_amd import level as LV
+    from gsv_tts_lite_amd import limiter as LM
+    from gsv_tts_lite_amd.stream import ChunkEmitter
+    from gsv_tts_lite_amd.track import TrackFormat, TrackResampler
+    ov, fmt = 640, TrackFormat(48000, 1, 20)
+    e = EQM.EQ([EQM.Band("highpass", 80.0), EQM.Band("peak", 300.0, q=1.0, gain_db=9.0)])
+    c = CM.Compressor(-30.0, 4.0, 1.0, 100.0, 3.0)
+    # in the chain's order: ChunkEmitter's keyword, the handle's record, the record's class, the stage on a device
+    stages = (("eq", "eq", EQM.EqStreamRecord, lambda d: EQM.StreamEQ(e, SR, d)),
+              ("compress", "comp", CM.CmpStreamRecord, lambda d: CM.StreamCompressor(c, SR, d)),
+              ("level", "level", LV.LevelRecord, lambda d: LV.StreamLeveller(-10.0, SR, d, seed=-30.0)),
+              ("limit", "limit", LM.StreamLimiterRecord, lambda d: LM.StreamLimiter(-6.0, SR, d)))
+    cases = []
+    for r in range(len(stages) + 1):
+        for subset in itertools.combinations(stages, r):
+            for tracked in (False, True):
+                em = ChunkEmitter(ov, track=TrackResampler(fmt, SR, dev) if tracked else None, **{s[0]: s[3](dev) for s in subset})
+                cases.append((em, subset, [s[3]("cpu") for s in subset], TrackResampler(fmt, SR, "cpu") if tracked else None))
+    assert len(cases) == 32 and not cases[0][1] and cases[0][0].track is None
+    sig = facade_audio(300, 40000, 0, 0, 0.5)
+    sm = np.convolve(sig, np.ones(5, np.float32) / 5, mode="same").astype(np.float32)
+    # (start, samples, final, first of its segment, mute, flush)
+    pushes = [(0, 3001, False, True, 0, False), (2361 - 13, 3002, False, False, 0, False), (4710 - 200, 3001, True, False, 1233, False),
+              (9000, 3001, True, True, 0, True)]
+    assert [(4 + n + m) & 1 for _, n, _, _, m, _ in pushes] == [1, 0, 0, 1]
+    handles = []
+    for start, n, final, first, mute, flush in pushes:
+        chunk = torch.from_numpy(sm[start: start + n].copy()).to(dev)
+        if first:
+            for em, _, _, _ in cases:
+                em.new_segment()
+        handles.append([em.push(chunk[None, None], final, trim_head=first, mute_samples=mute, flush=flush) for em, _, _, _ in cases])
+    same = lambda p, q, cls: type(p) is cls and all(getattr(p, f) == getattr(q, f) for f in cls.__slots__)
+    emitted = np.zeros(len(cases), np.int64)
+    for i, ((_, n, final, _, mute, flush), row) in enumerate(zip(pushes, handles)):
+        plain = row[0].result()
+        assert len(plain) == 3 and plain[0].dtype == np.float32 and len(plain[0]) > 0
+        for j, (h, (em, subset, host, h_track)) in enumerate(zip(row, cases)):
+            got = h.result()
+            assert len(got) == (3 if h_track is None else 4) and got[1:3] == plain[1:3], (i, j)
+            want = plain[0]
+            for (_, attr, cls, _), stage in zip(subset, host):
+                want = stage.push(want, flush)
+                assert same(getattr(h, attr), stage.rec, cls), (i, j, attr, getattr(h, attr), stage.rec)
+            assert got[0].dtype == np.float32 and got[0].tobytes() == want.tobytes(), (i, j)
+            assert all(getattr(h, s[1]) is None for s in stages if s not in subset), (i, j)
+            if h_track is not None:
+                assert np.array_equal(got[3], h_track.push(want, flush)), (i, j)
+            emitted[j] += len(got[0])
+    assert np.all(emitted == emitted[0])        # the flush hands out what a limiter held back
