@@ -13,10 +13,11 @@
 // writing the outputs that were not emitted before.  The open chunk is redone from its kept start state on every push.  Nothing
 // is continued by a recurrence of its own: the p behind a chunk as the full pass leaves it is not, in general, the bits
 // cmp_combine(JR, 0, st, B, C) gives, and only the chain's value may start the next chunk.  The operations are the same because
-// they are the same text: a span is compressor.h's cmp_span<PASS> (cmp_span_host in the twin), a link of the chain its
-// cmp_combine, the gain and the product its cmp_gain and cmp_out.  What is the stream's own -- the plan of a push, where a
-// sample comes from, how it enters the detector, which outputs are written, the record -- is one __host__ __device__ text for
-// the kernels, for the host twin cms_push_host (gsv_cmpstream_push_host: the CPU path and the device's oracle) and for
+// they are the same text, compressor.h's: a block of the kernel is cmp_open, cmp_body per span (cmp_span, the products, the
+// run's statistics) and cmp_close, a chain is cmp_chain_walk from the kept state, and the twin is cmp_drive_host and
+// cmp_walk_host over the stream's samples.  What is the stream's own -- the plan of a push, where a sample comes from, how it
+// enters the detector, which samples count and which outputs are written, the record -- is one __host__ __device__ text for the
+// kernels, for the host twin cms_push_host (gsv_cmpstream_push_host: the CPU path and the device's oracle) and for
 // tools/cmpstream_host_check.cpp.
 //
 // A sample that is not finite.  A clip holding one comes back unchanged, which a stream cannot know ahead of time; here (as in
@@ -138,17 +139,6 @@ LOUD_HD CmsRecord cms_bad_record() {
     return r;
 }
 
-// one link of a chain: the state in front of the next chunk from the state `st` in front of this one.  stage 0: p, from the
-// chunk's (B, C); 1: e, from its eend -- the operations of cmp_chain_host and cmp_chain_kernel
-LOUD_HD double cms_link(const CmpDesign& D, int stage, double st, const CmpChunk& c) {
-    if (stage == 0) {
-        double B = c.B, C = c.C;
-        cmp_combine(D.JR, 0.0, st, B, C);
-        return C;
-    }
-    return fma(D.JA, st, c.eend);
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // host only
 // ------------------------------------------------------------------------------------------------------------------
@@ -160,45 +150,6 @@ inline void cms_init_host(unsigned char* state, const CmpParams& d) {
     h.gmin_run = h.acc_gmin = CMP_ONE_BITS;
     memcpy(state, &h, sizeof h);
     cmp_design(d, reinterpret_cast<CmpDesign*>(state + cms_design_off()));
-}
-
-// the samples [lo, hi) of the stream (inside one chunk, lo its first sample) span by span from carry = {B, p, e}, as one block
-// walks them -> carry behind them.  pass 0 and 1: over a whole chunk, nothing written; 2: the outputs of the samples at or behind
-// N0, the three statistics' bits, the flags, and with stash_new the chunk's input as it came
-inline void cms_chunk_host(const float* stash_old, const float* chunk, long long N0, long long lo, long long hi, const CmpDesign& D, int pass,
-                           double* carry, float* out, float* stash_new, CmsHeader* h) {
-    static thread_local double v[CMP_T][CMP_R];
-    for (long long s0 = lo; s0 < hi; s0 += CMP_SPAN) {
-        const int cnt = hi - s0 < CMP_SPAN ? (int)(hi - s0) : CMP_SPAN;
-        for (int k = 0; k < CMP_SPAN; ++k) {
-            float xv = 0.f;
-            if (k < cnt) {
-                const float raw = cms_raw(stash_old, chunk, N0, lo, s0 + k);
-                if (stash_new) stash_new[s0 + k - lo] = raw;
-                xv = cms_enter(raw);
-                if (pass == 2 && s0 + k >= N0) {
-                    const uint32_t a = loud_abs_bits(raw);
-                    if (!cms_finite(raw)) h->acc_flags |= CMS_NONFINITE;
-                    else if (a > h->acc_in) h->acc_in = a;
-                }
-            }
-            v[k / CMP_R][k % CMP_R] = (double)xv;
-        }
-        cmp_span_host(D, pass, v, carry);
-        for (int k = 0; pass == 2 && k < cnt; ++k) {
-            if (s0 + k < N0) continue;          // emitted by an earlier push
-            const float raw = chunk[s0 + k - N0];       // out may be the chunk: read before the write
-            float o = raw;
-            if (cms_finite(raw)) {
-                const double g = v[k / CMP_R][k % CMP_R];
-                o = cmp_out(D.M, g, raw);
-                const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)g);
-                if (a > h->acc_out) h->acc_out = a;
-                if (gb < h->acc_gmin) h->acc_gmin = gb;
-            }
-            out[s0 + k - N0] = o;
-        }
-    }
 }
 
 // one push over host memory: the serial twin of the six launches.  out holds n floats and may be the chunk.
@@ -216,33 +167,38 @@ inline void cms_push_host(unsigned char* state, const float* chunk, int n, bool 
     float* stash_new = stash + (size_t)(1 - h.parity) * CMP_CHUNK;
     CmpChunk* ch = reinterpret_cast<CmpChunk*>(state + cms_scratch_off());
     const CmsPlan pl = cms_plan(h.n, n);
-    for (int b = 0; b < pl.done; ++b) {
-        const long long lo = (pl.k0 + b) * CMP_CHUNK;
-        double carry[3] = {0.0, 0.0, 0.0};
-        cms_chunk_host(stash_old, chunk, pl.N0, lo, lo + CMP_CHUNK, D, 0, carry, nullptr, nullptr, nullptr);
-        ch[b].B = carry[0]; ch[b].C = carry[1];
-    }
-    double st = open->pstart;
-    for (int b = 0; b <= pl.done; ++b) {
-        ch[b].pstart = st;
-        if (b < pl.done) st = cms_link(D, 0, st, ch[b]);
-    }
-    for (int b = 0; b < pl.done; ++b) {
-        const long long lo = (pl.k0 + b) * CMP_CHUNK;
-        double carry[3] = {0.0, ch[b].pstart, 0.0};
-        cms_chunk_host(stash_old, chunk, pl.N0, lo, lo + CMP_CHUNK, D, 1, carry, nullptr, nullptr, nullptr);
-        ch[b].eend = carry[2];
-    }
-    st = open->estart;
-    for (int b = 0; b <= pl.done; ++b) {
-        ch[b].estart = st;
-        if (b < pl.done) st = cms_link(D, 1, st, ch[b]);
-    }
+    const long long N0 = pl.N0, lo0 = pl.k0 * CMP_CHUNK;        // a sample in front of N0 lies in chunk k0: the stash's
+    const auto raw = [&](long long s) { return cms_raw(stash_old, chunk, N0, lo0, s); };
+    cmp_drive_host(D, lo0, pl.done, open->pstart, open->estart, ch, [&](long long s) { return cms_enter(raw(s)); });
+    // the full pass: the outputs of the samples at or behind N0, the three statistics' bits, the flags, and over the chunk left
+    // open its input as it came
     for (int b = 0; b < pl.nb; ++b) {
-        const long long lo = (pl.k0 + b) * CMP_CHUNK;
+        const long long lo = lo0 + (long long)b * CMP_CHUNK;
         const bool left_open = lo + CMP_CHUNK > pl.N1;
         double carry[3] = {0.0, ch[b].pstart, ch[b].estart};
-        cms_chunk_host(stash_old, chunk, pl.N0, lo, left_open ? pl.N1 : lo + CMP_CHUNK, D, 2, carry, out, left_open ? stash_new : nullptr, &h);
+        cmp_walk_host(
+            D, 2, lo, left_open ? pl.N1 : lo + CMP_CHUNK, carry,
+            [&](long long s) {
+                const float r = raw(s);
+                if (left_open) stash_new[s - lo] = r;
+                if (s >= N0) {
+                    const uint32_t a = loud_abs_bits(r);
+                    if (!cms_finite(r)) h.acc_flags |= CMS_NONFINITE;
+                    else if (a > h.acc_in) h.acc_in = a;
+                }
+                return cms_enter(r);
+            },
+            [&](long long s, double g) {
+                if (s < N0) return;                     // emitted by an earlier push
+                float o = chunk[s - N0];                // out may be the chunk: read before the write
+                if (cms_finite(o)) {
+                    o = cmp_out(D.M, g, o);
+                    const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)g);
+                    if (a > h.acc_out) h.acc_out = a;
+                    if (gb < h.acc_gmin) h.acc_gmin = gb;
+                }
+                out[s - N0] = o;
+            });
     }
     open->pstart = flush ? 0.0 : ch[pl.done].pstart;
     open->estart = flush ? 0.0 : ch[pl.done].estart;
@@ -259,9 +215,10 @@ __device__ __forceinline__ int cms_len_dev(const int32_t* n_dev, int n_cap) { re
 // cmp_kernel for a push: one block per chunk of the stream that the push touches, block b on chunk k0 + b.  PASS 0 and 1 run over
 // the chunks the push completes and write their scratch fields alone; PASS 2 runs over all it touches from the true start states:
 // the outputs of the push's own samples, the three statistics, the flags, and -- the block of the chunk left open -- the chunk's
-// input so far into the other stash.  Block shape, the padded runs in LDS and the barriers are cmp_kernel's, and cmp_span runs
-// over them.  The runs are staged as they came; the thread that owns a run then zeroes what is not finite in it (its own slots,
-// which no other thread reads before the barrier behind cmp_span) and so knows which of its gains do not count.
+// input so far into the other stash.  The block's frame is compressor.h's: cmp_open, per span cmp_body between the barriers
+// cmp_span states, cmp_close.  The kernel's own: the runs are staged as they came (cms_raw, into cmp_slot); the thread that owns a
+// run then zeroes what is not finite in it (its own slots, which no other thread reads before the barrier behind cmp_body) and
+// tells cmp_body which of its samples count: inside the span, at or behind N0, finite.
 // chunk and out may be one buffer: a block reads a span (and stashes it) before it writes the span's outputs, and no block reads
 // another block's samples.
 template <int PASS>
@@ -285,14 +242,8 @@ static __global__ __launch_bounds__(CMP_T) void cms_kernel(unsigned char* state,
     const long long lo = (pl.k0 + blk) * CMP_CHUNK, chunk_hi = lo + CMP_CHUNK;
     const long long hi = chunk_hi < pl.N1 ? chunk_hi : pl.N1;
     const bool left_open = PASS == 2 && chunk_hi > pl.N1;
-    if (tid < 3) stat_s[tid] = tid == 2 ? CMP_ONE_BITS : 0u;
-    if (tid == 0) {
-        flags_s = 0;
-        carry_s[0] = 0.0;
-        carry_s[1] = PASS == 0 ? 0.0 : ch->pstart;
-        carry_s[2] = PASS == 2 ? ch->estart : 0.0;
-    }
-    const double M = D->M;
+    cmp_open<PASS>(stat_s, carry_s, ch);
+    if (tid == 0) flags_s = 0;
     uint32_t peak_in = 0, peak_out = 0, gmin = CMP_ONE_BITS;
     int flags = 0;
     float* mine = xs + tid * (CMP_R + 1);
@@ -313,9 +264,9 @@ static __global__ __launch_bounds__(CMP_T) void cms_kernel(unsigned char* state,
                     else peak_in = a > peak_in ? a : peak_in;
                 }
             }
-            xs[(k / CMP_R) * (CMP_R + 1) + k % CMP_R] = xv;
+            xs[cmp_slot(k)] = xv;
         }
-        __syncthreads();                // xs, and carry_s of the last span (or of the prologue)
+        __syncthreads();                // xs, and carry_s of the last span (or of cmp_open)
         uint32_t own_nf = 0;            // bit i: sample i of this thread's run is not finite
 #pragma unroll
         for (int i = 0; i < CMP_R; ++i) {
@@ -325,22 +276,9 @@ static __global__ __launch_bounds__(CMP_T) void cms_kernel(unsigned char* state,
                 mine[i] = cms_enter(raw);
             }
         }
-        double v[CMP_R];
-        cmp_span<PASS>(D, mine, sc, carry_s, v);
+        const int r0 = tid * CMP_R;
+        cmp_body<PASS>(D, mine, sc, carry_s, cmp_run_bits(cnt - r0) & ~cmp_run_bits(N0 - s0 - r0) & ~own_nf, peak_out, gmin);
         if (PASS == 2) {
-            const int r0 = tid * CMP_R;
-            if (r0 < cnt) {
-#pragma unroll
-                for (int i = 0; i < CMP_R; ++i) {
-                    const float o = cmp_out(M, v[i], mine[i]);
-                    mine[i] = o;
-                    if (r0 + i < cnt && s0 + r0 + i >= N0 && !(own_nf >> i & 1u)) {
-                        const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)v[i]);
-                        peak_out = a > peak_out ? a : peak_out;
-                        gmin = gb < gmin ? gb : gmin;
-                    }
-                }
-            }
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < CMP_R; ++j) {
@@ -348,26 +286,15 @@ static __global__ __launch_bounds__(CMP_T) void cms_kernel(unsigned char* state,
                 const long long s = s0 + k;
                 if (k < cnt && s >= N0) {       // what an earlier push emitted is not written again
                     // not finite: copied bit for bit (in place: still the sample as it came)
-                    out[s - N0] = nf >> j & 1u ? chunk[s - N0] : xs[(k / CMP_R) * (CMP_R + 1) + k % CMP_R];
+                    out[s - N0] = nf >> j & 1u ? chunk[s - N0] : xs[cmp_slot(k)];
                 }
             }
             if (nf) flags |= CMS_NONFINITE;
         }
         __syncthreads();        // the next span stages over xs and sc; carry_s is whole
     }
-    if (PASS == 0) {
-        if (tid == 0) { ch->B = carry_s[0]; ch->C = carry_s[1]; }
-        return;
-    }
-    if (PASS == 1) {
-        if (tid == 0) ch->eend = carry_s[2];
-        return;
-    }
-    atomicMax(&stat_s[0], peak_in);
-    atomicMax(&stat_s[1], peak_out);
-    atomicMin(&stat_s[2], gmin);
-    if (flags) atomicOr(&flags_s, flags);
-    __syncthreads();
+    if (PASS == 2 && flags) atomicOr(&flags_s, flags);
+    if (!cmp_close<PASS>(carry_s, ch, stat_s, peak_in, peak_out, gmin)) return;
     CmsHeader* hd = reinterpret_cast<CmsHeader*>(state);
     if (tid == 0) {             // integer extrema: the order of the chunks does not show
         if (stat_s[0]) atomicMax(&hd->acc_in, stat_s[0]);
@@ -377,8 +304,8 @@ static __global__ __launch_bounds__(CMP_T) void cms_kernel(unsigned char* state,
     }
 }
 
-// between the passes: one wave chains the chunks the push completes from the open chunk's kept state (cms_link) -> the start
-// state of every chunk the push touches, scratch[0 .. done].  STAGE 0: pstart from (B, C); STAGE 1: estart from eend.
+// between the passes: one wave chains the chunks the push completes from the open chunk's kept state (cmp_chain_walk, one round)
+// -> the start state of every chunk the push touches, scratch[0 .. done].  STAGE 0: pstart from (B, C); STAGE 1: estart from eend.
 template <int STAGE>
 static __global__ __launch_bounds__(CMS_LANES) void cms_chain_kernel(unsigned char* state, int n_cap, const int32_t* n_dev) {
     __shared__ CmpChunk in_s[2 * CMS_LANES];
@@ -397,11 +324,8 @@ static __global__ __launch_bounds__(CMS_LANES) void cms_chain_kernel(unsigned ch
     }
     __syncthreads();
     if (lane == 0) {
-        double st = STAGE == 0 ? open->pstart : open->estart;
-        for (int b = 0; b <= done; ++b) {
-            out_s[b] = st;
-            if (b < done) st = cms_link(*D, STAGE, st, in_s[b]);
-        }
+        cmp_chain_walk(STAGE == 0 ? D->JR : D->JA, STAGE, STAGE == 0 ? open->pstart : open->estart, done + 1, done,
+                       [&](int b) -> const CmpChunk& { return in_s[b]; }, [&](int b, double st) { out_s[b] = st; });
     }
     __syncthreads();
     for (int b = lane; b <= done; b += CMS_LANES) {

@@ -41,6 +41,12 @@
 // bit patterns only when the full pass is over, and such a clip comes back bit for bit.  The commit launch then writes the record
 // and, per clip, y or x into `out` (in place and copied: nothing).  At most six launches, whatever the batch and the lengths.
 //
+// One text for clip and stream: cmpstream.h is the second caller of each of these.  On the device a block is cmp_open, per span
+// cmp_body -- cmp_span and, in pass 2, the products and the run's statistics under a mask of the samples that count -- and
+// cmp_close, around the kernel's own staging and write-back (cmp_slot: the padded runs); lane 0 of a chain wave calls
+// cmp_chain_walk, which steps with cmp_link.  On the host cmp_walk_host is a chunk span by span (the caller says how a sample is
+// loaded and what becomes of its gain) and cmp_drive_host the passes 0 and 1 with both chains, through cmp_chain_walk too.
+//
 // Workspace: [CmpRow rows[B] | CmpDesign designs[D] | y fp32 [sum of n, each clip 4-float aligned] | CmpChunk [sum of chunks] |
 // stats u32 [3 B]: max |x| bits, max |y| bits, min gain bits].  Rows and designs are one upload.
 #pragma once
@@ -213,6 +219,32 @@ LOUD_HD CmpRecord cmp_finish(const CmpRow& row, uint32_t peak_in, uint32_t peak_
 // the samples of such a clip come from x, not from y
 LOUD_HD bool cmp_copied(const CmpRow& row, const CmpRecord& r) { return row.design < 0 || (r.flags & CMP_NONFINITE); }
 
+// one link of a chain: the state in front of the next chunk from the state `st` in front of chunk c.  stage 0: p, from the chunk's
+// (B, C) with J = aR^CMP_CHUNK; 1: e, from its eend with J = aA^CMP_CHUNK
+LOUD_HD double cmp_link(double J, int stage, double st, const CmpChunk& c) {
+    if (stage == 0) {
+        double B = c.B, C = c.C;
+        cmp_combine(J, 0.0, st, B, C);
+        return C;
+    }
+    return fma(J, st, c.eend);
+}
+
+// the chain: from the state `st` in front of the first of cnt chunks, of which the first `links` have a successor, out(c, state in
+// front of chunk c) for every chunk -> the state behind the last link.  in(c) gives chunk c's (B, C) or eend and is asked for
+// chunks that have a successor alone: the fields of the others were never written
+template <class In, class Out>
+LOUD_HD double cmp_chain_walk(double J, int stage, double st, int cnt, int links, In in, Out out) {
+    for (int c = 0; c < cnt; ++c) {
+        out(c, st);
+        if (c < links) st = cmp_link(J, stage, st, in(c));
+    }
+    return st;
+}
+
+// a run's samples [0, n) as bits, n clamped to the run: which of its CMP_R samples count
+LOUD_HD uint32_t cmp_run_bits(long long n) { return n >= CMP_R ? (1u << CMP_R) - 1u : n > 0 ? (1u << n) - 1u : 0u; }
+
 // ------------------------------------------------------------------------------------------------------------------
 // host only: the checks, the workspace layout, the powers, the serial twin
 // ------------------------------------------------------------------------------------------------------------------
@@ -335,48 +367,40 @@ inline void cmp_span_host(const CmpDesign& D, int pass, double (*v)[CMP_R], doub
     }
 }
 
-// the samples [lo, hi) of a clip span by span as one block walks them, from carry = {B, p, e} -> carry behind them; pass 2
-// writes y and gathers the three statistics
-inline void cmp_chunk_host(const float* x, int lo, int hi, const CmpDesign& D, int pass, double* carry, float* y, uint32_t* stats) {
+// the runs of a span for cmp_walk_host: one buffer for all its forms
+inline double (*cmp_runs_host())[CMP_R] {
     static thread_local double v[CMP_T][CMP_R];
-    for (int s0 = lo; s0 < hi; s0 += CMP_SPAN) {
-        const int cnt = hi - s0 < CMP_SPAN ? hi - s0 : CMP_SPAN;
-        for (int k = 0; k < CMP_SPAN; ++k) {
-            float xv = 0.f;
-            if (k < cnt) {
-                xv = x[s0 + k];
-                const uint32_t a = loud_abs_bits(xv);
-                if (pass == 2 && a > stats[0]) stats[0] = a;
-            }
-            v[k / CMP_R][k % CMP_R] = (double)xv;
-        }
+    return v;
+}
+
+// the samples [lo, hi) of a signal span by span as one block walks them (inside one chunk, lo a span's first sample), from
+// carry = {B, p, e} -> carry behind them.  load(s) gives sample s as it enters the detector; in pass 2, gain(s, g) takes its
+// gain, after every load of the span
+template <class Load, class Gain>
+inline void cmp_walk_host(const CmpDesign& D, int pass, long long lo, long long hi, double* carry, Load load, Gain gain) {
+    double(*v)[CMP_R] = cmp_runs_host();
+    for (long long s0 = lo; s0 < hi; s0 += CMP_SPAN) {
+        const int cnt = hi - s0 < CMP_SPAN ? (int)(hi - s0) : CMP_SPAN;
+        for (int k = 0; k < CMP_SPAN; ++k) v[k / CMP_R][k % CMP_R] = k < cnt ? (double)load(s0 + k) : 0.0;
         cmp_span_host(D, pass, v, carry);
-        for (int k = 0; pass == 2 && k < cnt; ++k) {
-            const double g = v[k / CMP_R][k % CMP_R];
-            const float o = cmp_out(D.M, g, x[s0 + k]);
-            const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)g);
-            if (a > stats[1]) stats[1] = a;
-            if (gb < stats[2]) stats[2] = gb;
-            y[s0 + k] = o;
-        }
+        for (int k = 0; pass == 2 && k < cnt; ++k) gain(s0 + k, v[k / CMP_R][k % CMP_R]);
     }
 }
 
-// what the chain wave does (cmp_chain_kernel below) over the nch chunks of a clip; stage 0: pstart from (B, C), 1: estart from eend
-inline void cmp_chain_host(const CmpDesign& D, int stage, int nch, CmpChunk* ch) {
-    double st = 0.0;
-    for (int c = 0; c < nch; ++c) {
-        if (stage == 0) {
-            ch[c].pstart = st;
-            if (c + 1 < nch) {      // the last chunk's (B, C) were never written
-                double B = ch[c].B, C = ch[c].C;
-                cmp_combine(D.JR, 0.0, st, B, C);
-                st = C;
-            }
-        } else {
-            ch[c].estart = st;
-            if (c + 1 < nch) st = fma(D.JA, st, ch[c].eend);
+// what the passes 0 and 1 and the chain waves do over `done` whole chunks, the first one at sample lo, from the states (p0, e0)
+// in front of it: ch[0 .. done - 1] get (B, C) and eend, ch[0 .. done] pstart and estart.  Pass 2 is the caller's.
+template <class Load>
+inline void cmp_drive_host(const CmpDesign& D, long long lo, int done, double p0, double e0, CmpChunk* ch, Load load) {
+    for (int stage = 0; stage < 2; ++stage) {
+        for (int b = 0; b < done; ++b) {
+            double carry[3] = {0.0, stage == 0 ? 0.0 : ch[b].pstart, 0.0};
+            cmp_walk_host(D, stage, lo + (long long)b * CMP_CHUNK, lo + (long long)(b + 1) * CMP_CHUNK, carry, load, [](long long, double) {});
+            if (stage == 0) { ch[b].B = carry[0]; ch[b].C = carry[1]; }
+            else ch[b].eend = carry[2];
         }
+        cmp_chain_walk(stage == 0 ? D.JR : D.JA, stage, stage == 0 ? p0 : e0, done + 1, done,
+                       [&](int c) -> const CmpChunk& { return ch[c]; },
+                       [&](int c, double st) { (stage == 0 ? ch[c].pstart : ch[c].estart) = st; });
     }
 }
 
@@ -399,22 +423,24 @@ inline void cmp_run_host(const float* x, const CmpClip* clips, int n_clips, cons
         if (r.design >= 0) {
             const CmpDesign& Dd = D[r.design];
             CmpChunk* ch = chunks + r.soff;
-            for (int k = 0; k + 1 < r.nch; ++k) {
-                double carry[3] = {0.0, 0.0, 0.0};
-                cmp_chunk_host(xc, k * CMP_CHUNK, (k + 1) * CMP_CHUNK, Dd, 0, carry, nullptr, nullptr);
-                ch[k].B = carry[0]; ch[k].C = carry[1];
-            }
-            cmp_chain_host(Dd, 0, r.nch, ch);
-            for (int k = 0; k + 1 < r.nch; ++k) {
-                double carry[3] = {0.0, ch[k].pstart, 0.0};
-                cmp_chunk_host(xc, k * CMP_CHUNK, (k + 1) * CMP_CHUNK, Dd, 1, carry, nullptr, nullptr);
-                ch[k].eend = carry[2];
-            }
-            cmp_chain_host(Dd, 1, r.nch, ch);
+            float* yc = yws + r.yoff;
+            cmp_drive_host(Dd, 0, r.nch - 1, 0.0, 0.0, ch, [&](long long s) { return xc[s]; });
+            const auto load = [&](long long s) {
+                const uint32_t a = loud_abs_bits(xc[s]);
+                if (a > st[0]) st[0] = a;
+                return xc[s];
+            };
+            const auto gain = [&](long long s, double g) {
+                const float o = cmp_out(Dd.M, g, xc[s]);
+                const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)g);
+                if (a > st[1]) st[1] = a;
+                if (gb < st[2]) st[2] = gb;
+                yc[s] = o;
+            };
             for (int k = 0; k < r.nch; ++k) {
                 const long long hi = (long long)(k + 1) * CMP_CHUNK;
                 double carry[3] = {0.0, ch[k].pstart, ch[k].estart};
-                cmp_chunk_host(xc, k * CMP_CHUNK, hi < r.n ? (int)hi : r.n, Dd, 2, carry, yws + r.yoff, st);
+                cmp_walk_host(Dd, 2, (long long)k * CMP_CHUNK, hi < r.n ? hi : r.n, carry, load, gain);
             }
         } else {
             for (int i = 0; i < r.n; ++i) {
@@ -495,9 +521,67 @@ __device__ __forceinline__ void cmp_span(const CmpDesign* __restrict__ D, const 
     }
 }
 
+// the slot of sample k of a span in LDS: each thread's run is padded by one float so the runs start in different banks
+__device__ __forceinline__ int cmp_slot(int k) { return (k / CMP_R) * (CMP_R + 1) + k % CMP_R; }
+
+// in front of a block's first span: the block's statistics and the carry in front of the chunk -- zero, but in PASS 1 and 2 the
+// pstart and in PASS 2 the estart of `from`, when there is one.  The barrier in front of the first cmp_body publishes them.
+template <int PASS>
+__device__ __forceinline__ void cmp_open(uint32_t* stat_s, double* carry_s, const CmpChunk* from) {
+    const int tid = threadIdx.x;
+    if (tid < 3) stat_s[tid] = tid == 2 ? CMP_ONE_BITS : 0u;
+    if (tid == 0) {
+        carry_s[0] = 0.0;
+        carry_s[1] = PASS > 0 && from ? from->pstart : 0.0;
+        carry_s[2] = PASS == 2 && from ? from->estart : 0.0;
+    }
+}
+
+// One span of a block, between "the runs are staged" and "the products stand in the runs": cmp_span, and in PASS 2 the run at
+// `mine` becomes the products and the samples whose bit is set in `counts` (bit i: sample i of the run) enter the thread's
+// peak_out and gmin (the bits of max |y| and min g).  A run with no bit set is left as it is: nothing of it is written or counted.
+// Barriers: cmp_span's, on entry and on return.
+template <int PASS>
+__device__ __forceinline__ void cmp_body(const CmpDesign* __restrict__ D, float* mine, double (*sc)[2][CMP_T], double* carry_s, uint32_t counts,
+                                         uint32_t& peak_out, uint32_t& gmin) {
+    double v[CMP_R];
+    cmp_span<PASS>(D, mine, sc, carry_s, v);
+    if (PASS < 2 || !counts) return;
+    const double M = D->M;
+#pragma unroll
+    for (int i = 0; i < CMP_R; ++i) {
+        const float o = cmp_out(M, v[i], mine[i]);
+        mine[i] = o;
+        const bool on = counts >> i & 1u;       // selects, no branch: the run's LDS reads and writes stay paired
+        const uint32_t a = on ? loud_abs_bits(o) : 0u, gb = on ? loud_abs_bits((float)v[i]) : CMP_ONE_BITS;
+        peak_out = a > peak_out ? a : peak_out;
+        gmin = gb < gmin ? gb : gmin;
+    }
+}
+
+// behind a block's last span and its barrier.  PASS 0 and 1 park what the carry holds in the chunk's fields -- (B, C), eend -- and
+// give false: the block is done.  PASS 2 folds the threads' statistics (the bits of max |x|, max |y|, min g) into stat_s, passes a
+// barrier and gives true: stat_s is the block's, for the kernel's own atomics.
+template <int PASS>
+__device__ __forceinline__ bool cmp_close(const double* carry_s, CmpChunk* ch, uint32_t* stat_s, uint32_t peak_in, uint32_t peak_out,
+                                          uint32_t gmin) {
+    if (PASS < 2) {
+        if (threadIdx.x == 0) {
+            if (PASS == 0) { ch->B = carry_s[0]; ch->C = carry_s[1]; }
+            else ch->eend = carry_s[2];
+        }
+        return false;
+    }
+    atomicMax(&stat_s[0], peak_in);
+    atomicMax(&stat_s[1], peak_out);
+    atomicMin(&stat_s[2], gmin);
+    __syncthreads();
+    return true;
+}
+
 // One block per chunk of a clip.  PASS 0 and 1 run over the chunks that have a successor and write their CmpChunk fields alone;
 // PASS 2 runs over all of them from the true start states: y, both peaks, the smallest gain.  The span is staged in LDS by
-// coalesced loads, each thread's run padded by one float so the runs start in different banks; y goes back through the same slots.
+// coalesced loads (cmp_slot); y goes back through the same slots.
 template <int PASS>
 static __global__ __launch_bounds__(CMP_T) void cmp_kernel(const float* __restrict__ x, const CmpRow* __restrict__ rows,
                                                            const CmpDesign* __restrict__ designs, float* __restrict__ yws,
@@ -529,13 +613,7 @@ static __global__ __launch_bounds__(CMP_T) void cmp_kernel(const float* __restri
     const CmpDesign* __restrict__ D = designs + row.design;
     CmpChunk* __restrict__ ch = chunks + row.soff + chunk;
     float* __restrict__ yc = yws + row.yoff;
-    if (tid < 3) stat_s[tid] = tid == 2 ? CMP_ONE_BITS : 0u;
-    if (tid == 0) {
-        carry_s[0] = 0.0;
-        carry_s[1] = PASS == 0 || chunk == 0 ? 0.0 : ch->pstart;       // a clip of one chunk was never walked
-        carry_s[2] = PASS == 2 && chunk > 0 ? ch->estart : 0.0;
-    }
-    const double M = D->M;
+    cmp_open<PASS>(stat_s, carry_s, chunk > 0 ? ch : nullptr);     // a clip of one chunk was never walked
     uint32_t peak_in = 0, peak_out = 0, gmin = CMP_ONE_BITS;
     float* mine = xs + tid * (CMP_R + 1);
     for (int s0 = lo; s0 < hi; s0 += CMP_SPAN) {
@@ -547,47 +625,23 @@ static __global__ __launch_bounds__(CMP_T) void cmp_kernel(const float* __restri
                 const uint32_t a = loud_abs_bits(xv);
                 peak_in = a > peak_in ? a : peak_in;
             }
-            xs[(k / CMP_R) * (CMP_R + 1) + k % CMP_R] = xv;
+            xs[cmp_slot(k)] = xv;
         }
-        __syncthreads();                // xs, and carry_s of the last span (or of the prologue)
-        double v[CMP_R];
-        cmp_span<PASS>(D, mine, sc, carry_s, v);
+        __syncthreads();                // xs, and carry_s of the last span (or of cmp_open)
+        cmp_body<PASS>(D, mine, sc, carry_s, cmp_run_bits(cnt - tid * CMP_R), peak_out, gmin);
         if (PASS == 2) {
-            if (tid * CMP_R < cnt) {
-#pragma unroll
-                for (int i = 0; i < CMP_R; ++i) {
-                    const float o = cmp_out(M, v[i], mine[i]);
-                    mine[i] = o;
-                    if (tid * CMP_R + i < cnt) {
-                        const uint32_t a = loud_abs_bits(o), gb = loud_abs_bits((float)v[i]);
-                        peak_out = a > peak_out ? a : peak_out;
-                        gmin = gb < gmin ? gb : gmin;
-                    }
-                }
-            }
             __syncthreads();
-            for (int k = tid; k < cnt; k += CMP_T) yc[s0 + k] = xs[(k / CMP_R) * (CMP_R + 1) + k % CMP_R];
+            for (int k = tid; k < cnt; k += CMP_T) yc[s0 + k] = xs[cmp_slot(k)];
         }
         __syncthreads();        // the next span stages over xs and sc; carry_s is whole
     }
-    if (PASS == 0) {
-        if (tid == 0) { ch->B = carry_s[0]; ch->C = carry_s[1]; }
-        return;
-    }
-    if (PASS == 1) {
-        if (tid == 0) ch->eend = carry_s[2];
-        return;
-    }
-    atomicMax(&stat_s[0], peak_in);
-    atomicMax(&stat_s[1], peak_out);
-    atomicMin(&stat_s[2], gmin);
-    __syncthreads();
+    if (!cmp_close<PASS>(carry_s, ch, stat_s, peak_in, peak_out, gmin)) return;
     if (tid < 2) atomicMax(&stats[3 * blockIdx.y + tid], stat_s[tid]);      // integer extrema: the order of the chunks does not show
     if (tid == 2) atomicMin(&stats[3 * blockIdx.y + 2], stat_s[2]);
 }
 
-// between the passes: one wave per clip walks its chunks, CMP_LANES at a time through LDS.  STAGE 0: pstart from (B, C); STAGE 1:
-// estart from eend, and the clip's statistics are cleared for pass 2.
+// between the passes: one wave per clip walks its chunks (cmp_chain_walk), CMP_LANES at a time through LDS.  STAGE 0: pstart from
+// (B, C); STAGE 1: estart from eend, and the clip's statistics are cleared for pass 2.
 template <int STAGE>
 static __global__ __launch_bounds__(CMP_LANES) void cmp_chain_kernel(const CmpRow* __restrict__ rows, const CmpDesign* __restrict__ designs,
                                                                      CmpChunk* __restrict__ chunks, uint32_t* __restrict__ stats) {
@@ -607,18 +661,14 @@ static __global__ __launch_bounds__(CMP_LANES) void cmp_chain_kernel(const CmpRo
         }
         __syncthreads();
         if (lane == 0) {
-            for (int c = 0; c < cnt; ++c) {
-                out_s[c] = st;
-                if (base + c + 1 < row.nch) {
-                    if (STAGE == 0) {
-                        double B = in_s[0][c], C = in_s[1][c];
-                        cmp_combine(J, 0.0, st, B, C);
-                        st = C;
-                    } else {
-                        st = fma(J, st, in_s[0][c]);
-                    }
-                }
-            }
+            st = cmp_chain_walk(J, STAGE, st, cnt, row.nch - 1 - base,
+                                [&](int c) {
+                                    CmpChunk k = {};
+                                    k.B = k.eend = in_s[0][c];
+                                    if (STAGE == 0) k.C = in_s[1][c];
+                                    return k;
+                                },
+                                [&](int c, double v) { out_s[c] = v; });
         }
         __syncthreads();
         if (lane < cnt) {
